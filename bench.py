@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — TPC-H Q1 hash-aggregation throughput (rows/s) on synthetic lineitem, SF100 (BASELINE.json's metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--sf 100]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--sf 100] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the Q1 pipeline (filter -> decimal maps -> partial hash aggregation) over one rank's lineitem
 shard that is already resident in HBM, followed by the partial-state exchange over RCCL when N > 1 and the final merge.
@@ -11,13 +11,21 @@ shard that is already resident in HBM, followed by the partial-state exchange ov
          partial-state row to rank hash % N on the device (dbhip_groupby_partition_blocks) and exchanges them with one
          all_to_all_single; `--exchange allgather` all-gathers the blocks and merges everything on every rank.
 The lineitem shard is generated on the device (databend_amd.tpch.LineitemTorch: torch is plumbing; identical data for
-every N). Prints ONE JSON line (rank 0) with the contract fields plus
-  roofline       q1_fused_kernel, HIP events on its launch stream, 68 B/row algorithmic
+every N). A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the contract fields plus
+  roofline       the headline kernel, HIP events on its launch stream during the timed steps, 68 B/row algorithmic
+--dump-outputs DIR writes rank 0's Q1 result table of the last timed step as .npy files (dump_outputs). --full adds every
+secondary measurement and check below (each still has its --no-* switch):
+  hand_written_kernel / exchange_impl_other  the other kernel (N = 1) or the other exchange implementation (N > 1) beside the
+                 headline, same steps, same result; N > 1: the exchanged result against the ranks' un-exchanged local states
+  multi_gpu_readiness  one rank's step of the 8-GPU job (SF100/8) with the C-ABI's exchange on a local world of one
   cpu_baseline   the reference-shaped CPU Q1 (oracle/q1_typed.c) timed on the host cores over a stated sample,
                  and used as the checker of the device result (sample AND the whole table, chunk by chunk)
   q1_operator_plan  the SAME query through the generic operator kernels (what a drop-in dispatches to), ms + fraction
   q3_sf100       BASELINE configs[2] (tools/bench_q3.py's plan) in the same process
+  distributed_plan_stages  one rank's stages of the distributed sort and of the shuffle join (tools/bench_dist_sort.py)
+  scan_side_zstd Q1's seven columns as ZSTD Parquet pages decoded on the device (tools/pq_scan_probe.py)
   ann            BASELINE configs[4]
+  q1_block_size_sweep  Q1 fed as blocks through the C-ABI (databend_amd/host/block_sweep)
 """
 import argparse
 import ctypes as C
@@ -99,7 +107,12 @@ def main():
     ap.add_argument("--exchange-impl", choices=["torch", "abi"], default="torch",
                     help="N > 1: who owns the communicator of the partial-state exchange: torch.distributed (default), or the C-ABI's "
                          "own RCCL communicator (dbhip_comm_*, dbhip_groupby_exchange_*: what a Rust host would call)")
+    ap.add_argument("--full", action="store_true", help="also run the secondary measurements and checks (module docstring); "
+                    "off: set up, warm up, time --steps steps, dump, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write rank 0's Q1 result of the last timed step to DIR/*.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args, sys.argv[1:])       # does not return
@@ -165,7 +178,7 @@ def main():
     # timed right after it (same steps) and reported beside it (`exchange_impl_other`): torch.distributed's collectives on the
     # library's buffers, and the C-ABI's own communicator (dbhip_comm_*: what a Rust host would call). (Ranks that SHARE a GPU cannot
     # form an RCCL communicator — RCCL refuses duplicate devices — so `--share-gpu` runs the selected implementation only.)
-    both_impls = world > 1 and args.backend == "nccl" and not args.share_gpu
+    both_impls = args.full and world > 1 and args.backend == "nccl" and not args.share_gpu
     abi_handle = None
     if world > 1 and (args.exchange_impl == "abi" or both_impls):
         ids = [D.Comm.unique_id() if rank == 0 else None]
@@ -227,6 +240,8 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, tpch.q1_rows(g))
 
     # the OTHER exchange implementation, same steps, same barriers (N > 1 over RCCL only)
     other_impl = None
@@ -257,7 +272,7 @@ def main():
         other_impl["equals_headline_result"] = other_impl.pop("_rows") == result_headline
     # the OTHER kernel beside it, same rows, same steps: its per-launch duration and wall time
     other = None
-    if world == 1:
+    if args.full and world == 1:
         okms = []
         g2 = D.GroupBy.q1()
 
@@ -294,7 +309,7 @@ def main():
     value = n_total * args.steps / dt
     result = tpch.q1_rows(g)
     n_groups = len(result)
-    if world > 1:
+    if args.full and world > 1:
         # the exchanged result against the un-exchanged local states: count(*) summed over the ranks, and every aggregate
         # of every group summed over the ranks (allgather: every rank holds everything, so the sums are world x the local
         # sums; alltoall: rank r holds the groups with hash % world == r, once)
@@ -319,37 +334,38 @@ def main():
             x = t.tolist()
             return [x[i] + (x[i + 1] << 42) + (x[i + 2] << 84) for i in range(0, len(x), 3)]
         assert [v * mult for v in ints(exp)] == ints(got), "exchange lost or duplicated partial states"
+    if world > 1:
         ng = torch.tensor([len(result)], dtype=torch.int64, device="cuda")
         dist.all_reduce(ng, op=dist.ReduceOp.SUM if exchange == "alltoall" else dist.ReduceOp.MAX)
         n_groups = int(ng.item())
 
     readiness = None
-    if world == 1 and rank == 0 and n_total >= 8 * (1 << 20) and not args.no_readiness:
+    if args.full and world == 1 and rank == 0 and n_total >= 8 * (1 << 20) and not args.no_readiness:
         readiness = bench_exchange_overhead(li, n_total // 8 & ~3, tpch, D, L, check, args.steps)
 
     opplan = None
-    if not args.no_opplan and world == 1:
+    if args.full and not args.no_opplan and world == 1:
         opplan = bench_operator_plan(li, tpch, D, L, check, result, kernel_ms)
 
     cpu = None
-    if rank == 0 and not args.no_cpu and world == 1:
+    if args.full and rank == 0 and not args.no_cpu and world == 1:
         cpu = cpu_baseline(args, li, n, tpch, result)
 
     q3 = None
     ann = None
     del li  # the lineitem shard is not needed any more: give its HBM back
     torch.cuda.empty_cache()
-    if not args.no_q3 and world == 1:
+    if args.full and not args.no_q3 and world == 1:
         q3 = bench_q3(args, torch, tpch, D, L, check)
         torch.cuda.empty_cache()
-    elif not args.no_q3:
+    elif args.full and not args.no_q3:
         try:      # (a secondary measurement never takes the headline line down)
             q3 = bench_q3_dist(args, rank, world, torch, dist, tpch, D, DX, L, check)
         except Exception as e:  # noqa: BLE001
             q3 = {"error": repr(e)}
         torch.cuda.empty_cache()
     plans = None
-    if world == 1 and not args.no_readiness:
+    if args.full and world == 1 and not args.no_readiness:
         # one rank's stages of the distributed sort and of the shuffle join's scatter (SURVEY §8e rows "sort" / "hash join") at 60 M rows
         try:
             sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -359,7 +375,7 @@ def main():
             plans = {"error": repr(e)}
         torch.cuda.empty_cache()
     scan = None
-    if not args.no_scan and world == 1:
+    if args.full and not args.no_scan and world == 1:
         # the scan side in front of the hot path: Q1's seven lineitem columns as the reference's writer lays them out —
         # ZSTD level 1 (its default codec), DATA_PAGE_V2, 20 000-row pages — 8 blocks of 6 M rows decoded by ONE dbhip_pq_chunks_decode_device
         # call from the stored bytes resident in HBM; the decode is checked to be the identity on what was written
@@ -371,7 +387,7 @@ def main():
         except Exception as e:      # a secondary measurement never takes the headline line down
             scan = {"error": repr(e)}
         torch.cuda.empty_cache()
-    if not args.no_ann:
+    if args.full and not args.no_ann:
         ann = bench_ann(args, rank, world, torch, dist, D, DX, L, check)
         if world == 1 and not args.no_hnsw:
             # the reference's own indexed path beside the exact index: HNSW (m=10, ef_construct=40, ef=4k) over u8-quantised
@@ -385,7 +401,7 @@ def main():
             ann["hnsw_reference_mode_clustered"] = BH.run(rows=args.hnsw_rows, dim=args.ann_dim, queries=10_000, k=10, clusters=1024, normalize=True)
 
     blocks = None
-    if rank == 0 and world == 1 and not args.no_blocks:
+    if args.full and rank == 0 and world == 1 and not args.no_blocks:
         blocks = bench_block_sizes(cpu)
     if rank == 0:
         achieved = (n * BYTES_PER_ROW) / (kernel_ms * 1e-3) / 1e9 if kernel_ms else 0.0
@@ -434,6 +450,26 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+Q1_COLUMNS = ("returnflag", "linestatus", "sum_qty", "sum_base_price", "sum_disc_price", "sum_charge", "sum_disc", "count")
+
+
+def dump_outputs(out_dir, rows):
+    """--dump-outputs: the Q1 group table a caller of the timed path reads back (GroupBy.result(), one row per (returnflag,
+    linestatus) group), ordered by the two keys, as float64 [groups x Q1_COLUMNS]:
+      q1_result.npy           the key bytes and the aggregates as numbers (decimals unscaled: sum_qty 2, sum_base_price 2,
+                              sum_disc_price 4, sum_charge 6, sum_disc 2 fractional digits)
+      q1_result_residual.npy  value - q1_result per cell: the 128-bit sums outgrow float64's 53 bits, and the pair holds
+                              every value exactly (value == int(q1_result) + int(q1_result_residual))"""
+    import numpy as np
+    exact = [[k[0][0], k[1][0]] + [int(rows[k][c]) for c in Q1_COLUMNS[2:]] for k in sorted(rows)]
+    approx = np.array(exact, dtype=np.float64).reshape(len(exact), len(Q1_COLUMNS))
+    residual = np.array([[v - int(a) for v, a in zip(r, ra)] for r, ra in zip(exact, approx)], dtype=np.float64).reshape(approx.shape)
+    assert all(int(a) + int(b) == v for r, ra, rb in zip(exact, approx, residual) for v, a, b in zip(r, ra, rb))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "q1_result.npy"), approx)
+    np.save(os.path.join(out_dir, "q1_result_residual.npy"), residual)
 
 
 def bench_exchange_overhead(li, n_shard, tpch, D, L, check, steps):

@@ -48,11 +48,12 @@ def test_world_size_must_equal_gpus():
 @pytest.mark.gpu
 def test_two_ranks_start_themselves_on_a_shared_gpu():
     """`python bench.py --gpus 2` with NO launcher around it: two ranks come up (gloo, both on cuda:0), run the row-range
-    sharded Q1 with the all-to-all exchange of partial states, and rank 0 prints one line with n_gpus = 2."""
+    sharded Q1 with the all-to-all exchange of partial states (checked against the ranks' local states: --full), and rank 0
+    prints one line with n_gpus = 2."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu", "--steps", "2",
-                        "--warmup", "1", "--rows", "8000000", "--no-q3", "--no-ann", "--no-cpu"], env=env, capture_output=True, text=True,
-                       timeout=900)
+                        "--warmup", "1", "--rows", "8000000", "--full", "--no-q3", "--no-ann", "--no-cpu"], env=env, capture_output=True,
+                       text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1

@@ -3,7 +3,7 @@
 #   bash tools/gpu_run.sh <tag> <step> [<step> ...]
 # steps (each writes under gpurun_out/, named by <tag>):
 #   tests[:<pytest args>]     pytest -m gpu (default: the whole suite)
-#   bench[:<bench args>]      python bench.py <args>                  -> bench_<tag>.json
+#   bench[:<bench args>]      python bench.py <args> (--full: every secondary measurement) -> bench_<tag>.json
 #   prof[:<bench args>]       rocprofv3 --kernel-trace --stats of bench.py -> <tag>_kernel_stats.csv
 #   pmc:<C1,C2..>[:<bench args>]  one --pmc pass (kernel-trace only) of bench.py -> <tag>_pmc_<C1>.csv
 #   mb:<microbench args>      python tools/microbench.py <args>       -> mb_<tag>.json
