@@ -68,7 +68,7 @@ class AggDesc(C.Structure):
 
 
 def library_path():
-    # DBHIP_LIBRARY: another build of the same library (tools/probes A/B runs: an experiments build beside the shipped one)
+    # DBHIP_LIBRARY: another build of the same library (same-box A/B runs against an older commit's build)
     return os.environ.get("DBHIP_LIBRARY") or os.path.join(_HERE, "libdbhip.so")
 
 

@@ -142,8 +142,6 @@ struct ZWave {
   uint8_t* tab;
   uint32_t lane;
 
-  static constexpr bool RESOLVES_OFFSETS = false;   // zstd_core.h hands seq() the resolved offset
-  __device__ __forceinline__ bool seq_raw(uint32_t, uint32_t, uint32_t) { return false; }
   __device__ __forceinline__ bool lead() const { return lane == 0; }
   __device__ __forceinline__ void sync() const { __builtin_amdgcn_wave_barrier(); }
   __device__ __forceinline__ bool bcast(bool b) const { return __builtin_amdgcn_readfirstlane((int)b) != 0; }
@@ -154,16 +152,11 @@ struct ZWave {
   __device__ __forceinline__ uint64_t* mlt() const { return (uint64_t*)(tab + 8192); }
   __device__ __forceinline__ uint32_t* oft() const { return (uint32_t*)(tab + 12288); }
   __device__ __forceinline__ uint8_t* scr() const { return tab + 13312; }
-  // entry of a sequence table at a (uniform) state number
-  __device__ __forceinline__ uint64_t ll_at(uint32_t st) const { return llt()[st]; }
-  __device__ __forceinline__ uint64_t ml_at(uint32_t st) const { return mlt()[st]; }
-  __device__ __forceinline__ uint32_t of_at(uint32_t st) const { return oft()[st]; }
   // parking slots (zstd_core.h decode_frames): stored by lane 0, read back by the wave; volatile so that the value is really re-loaded
   __device__ __forceinline__ void park(uint32_t i, uint32_t v) const { if (lane == 0) ((volatile uint32_t*)(scr() + zc::SCR_PARK))[i] = v; }
   __device__ __forceinline__ uint32_t unpark(uint32_t i) const { return rfl(((volatile uint32_t*)(scr() + zc::SCR_PARK))[i]); }
   __device__ __forceinline__ uint32_t op() const { return op_; }
   __device__ __forceinline__ uint32_t cap() const { return cap_; }
-  __device__ __forceinline__ void frame_begin() { frame0 = op_; }
 
   // ---- the window (headers, table descriptions, backward bitstreams)
   __device__ __forceinline__ void slide(uint32_t wl) {
@@ -336,24 +329,6 @@ struct ZWave {
     if (FLUSH) advance(ll + ml);
     else op_ += ll + ml;           // (the caller has flushed and keeps to 64 of these: see zq_consume)
   }
-  // literals + match of one ZSTD sequence (ll > 0)
-  __device__ __forceinline__ bool put_seq(uint32_t ll, uint32_t off, uint32_t ml) {
-    if (ll <= 8 && ll + ml <= 64 && lit_kind != 2 && off <= WM - 127) {
-      if (ll > lit_left || ll + ml > cap_ - op_ || off == 0 || off > op_ - frame0 + ll) return false;
-      const uint64_t bits = lit.u64(lit_at);
-      lit_left -= ll;
-      lit_at = rfl(lit_at + ll);
-      pair_small(bits, ll, off, ml);
-      return true;
-    }
-    return put_lit(ll) && put_match(off, ml);
-  }
-  // one sequence of a ZSTD block (zstd_core.h): ll literals (possibly none), then ml bytes from `off` back
-  __device__ __forceinline__ bool seq(uint32_t ll, uint32_t off, uint32_t ml) { return ll ? put_seq(ll, off, ml) : put_match(off, ml); }
-  __device__ __forceinline__ uint32_t lit_rest() const { return lit_left; }
-  __device__ __forceinline__ int sequences(uint32_t p, uint32_t len, uint32_t nseq, uint32_t als, uint32_t& r0, uint32_t& r1, uint32_t& r2) {
-    return zc::seq_loop(*this, p, len, nseq, als, r0, r1, r2);
-  }
   template <bool CK = true>
   __device__ __forceinline__ bool put_lit(uint32_t len) {
     if (CK && (len > lit_left || len > cap_ - op_)) return false;
@@ -366,28 +341,6 @@ struct ZWave {
     }
     lit_at = rfl(lit_at + len);
     return true;
-  }
-
-  // THE COMMON SEQUENCE in one LDS round trip: up to 8 literal bytes that the caller holds as a scalar (`litbits`, byte i = bits [8 i, 8 i + 8))
-  // followed by a back-reference of `mlen` bytes, lit + mlen <= 64, the source inside the ring (1 <= off <= W - 128, off <= bytes written
-  // + lit: checked by the caller). Lane l < lit writes literal byte l; lane lit + m writes match byte m, whose source lies `off` back:
-  // either among the bytes already in the ring (one ds_read for all lanes) or among the literal bytes of this very sequence (taken from
-  // the scalar, no LDS access) — by periodicity out[x] = out[x - off (1 + floor(m / off))].
-  __device__ __forceinline__ void pair_small(uint64_t litbits, uint32_t lit, uint32_t off, uint32_t mlen) {
-    const int32_t m = (int32_t)lane - (int32_t)lit;                 // match byte index (negative: a literal lane)
-    uint32_t mm = m > 0 ? (uint32_t)m : 0u;
-    if (off < 64) {
-      const float r = __builtin_amdgcn_rcpf((float)off);          // mm mod off (see put_match)
-      mm = mm - off * (uint32_t)(((float)mm + 0.5f) * r);
-    }
-    const int32_t rel = (int32_t)lit - (int32_t)off + (int32_t)mm;  // source relative to op_: < 0 in the ring, >= 0 a literal of this sequence
-    const uint32_t from_ring = win[(op_ + (uint32_t)rel + sh) & WM];
-    const uint32_t li = m < 0 ? lane : (uint32_t)rel;             // which literal byte this lane takes if it takes one
-    const uint32_t from_lit = (uint32_t)(litbits >> (8 * (li & 7))) & 0xFF;
-    const uint32_t v = (m < 0 || rel >= 0) ? from_lit : from_ring;
-    if (lane < lit + mlen) win[(op_ + lane + sh) & WM] = (uint8_t)v;
-    __builtin_amdgcn_wave_barrier();
-    advance(lit + mlen);
   }
 
   // A BATCH OF m <= 64 SEQUENCES REPLAYED BY THE BYTE (round 6). Lane i < m holds sequence i: `ll` literals, then `ml` bytes from `off`
@@ -565,8 +518,8 @@ struct ZWave {
 // walks, three bit reads, the repeat-offset rules), then move its bytes — and one wave walking both halves took 28-30 ms for a
 // 160 KB page of 20 000 sequences. Here wave 0 of a 128-thread workgroup (the PRODUCER: ZProd) runs the whole format — headers,
 // tables, Huffman literals, the sequence bitstream — but executes nothing: it checks every command against its own count of the
-// output position and queues it; wave 1 (the CONSUMER) replays the commands against the ring with the executor of the one-wave
-// kernel. The queue is a single-producer / single-consumer ring in LDS: 64 commands collect in the producer's registers
+// output position and queues it; wave 1 (the CONSUMER) replays the commands against the ring with ZWave's executor (the one the
+// LZ4 / Snappy kernel uses). The queue is a single-producer / single-consumer ring in LDS: 64 commands collect in the producer's registers
 // (a compare and four selects per command), leave as one 16-byte LDS store per lane, and are taken 64 at a time (one LDS load per lane, v_readlane per
 // command); `tail` / `head` are LDS words written by one side each. Because the producer validates, the consumer cannot fail: it
 // always drains to the END command, the producer always sends one — neither wave can wait for something that will not come.
@@ -575,11 +528,7 @@ struct ZWave {
 // ---------------------------------------------------------------------------------------------
 constexpr uint32_t ZW_RING = 4096;                          // ZSTD: ring bytes (r06 sweep on the 7-column set, tools/probes/r06_zstd_ring.sh: 16 KiB 22.4 ms, 8 KiB 20.0, 4 KiB 16.8, 2 KiB 17.8 — pages per CU by LDS)
 constexpr uint32_t ZW_TABLES = 13312 + zc::SCR_BYTES;       // Huffman 4 KiB + LL 4 KiB + ML 4 KiB + OF 1 KiB + scratch
-constexpr uint32_t ZW_LDS = ZW_RING + ZW_TABLES;
-#ifndef DBHIP_ZQ_CAP
-#define DBHIP_ZQ_CAP 64
-#endif
-constexpr uint32_t ZQ_CAP = DBHIP_ZQ_CAP;    // commands in the queue (16 bytes each): ONE batch — the consumer takes a batch into registers and gives
+constexpr uint32_t ZQ_CAP = 64;              // commands in the queue (16 bytes each): ONE batch — the consumer takes a batch into registers and gives
                                              // the slots back before it executes it, the producer collects the next one in registers meanwhile
 constexpr uint32_t ZQ_BYTES = ZQ_CAP * 16 + 16;
 constexpr uint32_t ZW2_LDS = ZW_RING + ZW_TABLES + ZQ_BYTES;   // the two-wave kernel: + the command queue
@@ -610,7 +559,7 @@ constexpr uint32_t ZQ_POLLS = 1u << 24;
 // words of the collected commands), [1280, 1408) the scalars.
 __device__ __attribute__((noinline)) void zprod_sequences(uint32_t tab_lds);
 enum { ZH_SRC_LO = 0, ZH_SRC_HI, ZH_A0, ZH_SAFE, ZH_WLO, ZH_QN, ZH_QTAIL, ZH_OP, ZH_FRAME0, ZH_CAP, ZH_LIT_LEFT, ZH_VIOL, ZH_FAILED, ZH_R0, ZH_R1,
-       ZH_R2, ZH_P, ZH_LEN, ZH_NSEQ, ZH_ALS, ZH_RC, ZH_XW_LO, ZH_XW_HI, ZH_WORDS };
+       ZH_R2, ZH_P, ZH_LEN, ZH_NSEQ, ZH_ALS, ZH_RC, ZH_WORDS };
 static_assert(1280 + 4 * ZH_WORDS <= zc::SCR_PARK, "the hand-over block must fit the scratch area below the parking slots");
 
 struct ZProd : ZWave {
@@ -626,14 +575,6 @@ struct ZProd : ZWave {
   // consumer's, together with the repeat-offset history (seq_raw below).
   uint32_t viol;
   bool failed;                 // a batch was refused: every later call fails
-#ifdef DBHIP_EXPERIMENTS
-  uint64_t x_wait = 0;         // cycles spent waiting for the consumer (queue full / drain)
-#define ZX_T0 const uint64_t zx_t0 = __builtin_readcyclecounter();
-#define ZX_ADD(acc) acc += __builtin_readcyclecounter() - zx_t0;
-#else
-#define ZX_T0
-#define ZX_ADD(acc)
-#endif
 
   __device__ __forceinline__ void qbegin(const ZQueue& Q) { q = Q; qn = 0; qtail = 0; b0 = b1 = b2 = b3 = 0; viol = cap_ >> 31; failed = false; }
   __device__ __forceinline__ bool batch_ok() const {   // (selects between integers: a bool turned into an integer leaves the scalar unit)
@@ -645,13 +586,11 @@ struct ZProd : ZWave {
   // the collected commands -> the queue (waits for room), unchecked
   __device__ __forceinline__ void qsend() {
     if (qn == 0) return;
-    ZX_T0
     for (uint32_t polls = 0; qtail + qn - q.head() > ZQ_CAP; ++polls) {
       if (polls >= ZQ_POLLS) q.kill();
       if (q.dead()) { qn = 0; return; }
       __builtin_amdgcn_s_sleep(2);
     }
-    ZX_ADD(x_wait)
     if (lane < qn) q.slots[(qtail + lane) & (ZQ_CAP - 1)] = u32x4q{b0, b1, b2, b3};
     qtail = rfl(qtail + qn);
     qn = 0;
@@ -674,13 +613,11 @@ struct ZProd : ZWave {
   __device__ __forceinline__ void drain() {
     qflush();
     if (failed) return;
-    ZX_T0
     for (uint32_t polls = 0; q.done() != qtail; ++polls) {
       if (polls >= ZQ_POLLS) q.kill();
       if (q.dead()) return;
       __builtin_amdgcn_s_sleep(2);
     }
-    ZX_ADD(x_wait)
   }
 
   // ---- the output half of the interface zstd_core.h expects: validate against the producer's own position, queue, count
@@ -729,9 +666,6 @@ struct ZProd : ZWave {
     if (lane == 0) {
       H[ZH_WLO] = wlo; H[ZH_QN] = qn; H[ZH_QTAIL] = qtail; H[ZH_OP] = op_; H[ZH_LIT_LEFT] = lit_left; H[ZH_VIOL] = viol;
       H[ZH_FAILED] = failed ? 1u : 0u;
-#ifdef DBHIP_EXPERIMENTS
-      H[ZH_XW_LO] = (uint32_t)x_wait; H[ZH_XW_HI] = (uint32_t)(x_wait >> 32);
-#endif
     }
     hot_put_lanes();
   }
@@ -739,9 +673,6 @@ struct ZProd : ZWave {
     const uint32_t* H = hot_words();
     wlo = rfl(H[ZH_WLO]); qn = rfl(H[ZH_QN]); qtail = rfl(H[ZH_QTAIL]); op_ = rfl(H[ZH_OP]); lit_left = rfl(H[ZH_LIT_LEFT]);
     viol = rfl(H[ZH_VIOL]); failed = rfl(H[ZH_FAILED]) != 0;
-#ifdef DBHIP_EXPERIMENTS
-    x_wait = (uint64_t)rfl(H[ZH_XW_LO]) | ((uint64_t)rfl(H[ZH_XW_HI]) << 32);
-#endif
     hot_get_lanes();
   }
   __device__ __forceinline__ int sequences(uint32_t p, uint32_t len, uint32_t nseq, uint32_t als, uint32_t& r0, uint32_t& r1, uint32_t& r2) {
@@ -814,24 +745,18 @@ __device__ __attribute__((noinline)) void zprod_sequences(uint32_t tab_lds) {
 }
 
 // the consumer: replays the commands until END; -> the producer's status
-__device__ __forceinline__ uint32_t zq_consume(ZWave& w, const ZQueue& q, uint32_t xmode, uint64_t* xwait = nullptr) {
+__device__ __forceinline__ uint32_t zq_consume(ZWave& w, const ZQueue& q) {
   uint32_t head = 0;
   uint32_t r0 = 1, r1 = 4, r2 = 8;   // the repeat offsets of the frame being replayed
   uint32_t bad = 0;                  // an offset reached before its frame: nothing is executed from there on
   for (;;) {
     uint32_t tail = q.tail();
-#ifdef DBHIP_EXPERIMENTS
-    const uint64_t zx_c0 = __builtin_readcyclecounter();
-#endif
     for (uint32_t polls = 0; tail == head; ++polls) {
       if (polls >= ZQ_POLLS) q.kill();
       if (q.dead()) return (uint32_t)zc::CORRUPT_;
       __builtin_amdgcn_s_sleep(16);   // (a batch of 64 commands takes the producer ~10^5 cycles: a poll every ~1000 costs the CU's shared scalar unit next to nothing)
       tail = q.tail();
     }
-#ifdef DBHIP_EXPERIMENTS
-    if (xwait) *xwait += __builtin_readcyclecounter() - zx_c0;
-#endif
     const uint32_t m = rfl(tail - head < 64 ? tail - head : 64);
     const u32x4q e = q.slots[(head + (w.lane < m ? w.lane : 0)) & (ZQ_CAP - 1)];
     head = rfl(head + m);
@@ -839,10 +764,7 @@ __device__ __forceinline__ uint32_t zq_consume(ZWave& w, const ZQueue& q, uint32
     // THE COMMON BATCH: nothing but sequences — replayed BY THE BYTE, not by the sequence (ZWave::replay; one sequence per step made the
     // consumer the wave the page waited for). What is left to do here is the only serial part, phase A: the repeat-offset history
     // (RFC 8878 3.1.1.5) as one scalar pass over the batch without a memory access; the resolved offset of sequence i lands in lane i.
-    if (__builtin_amdgcn_ballot_w64(w.lane < m && e.z == 0) == 0 && !(xmode & 1)) {
-#ifdef DBHIP_EXPERIMENTS
-      if (xwait) xwait[1] += m;
-#endif
+    if (__builtin_amdgcn_ballot_w64(w.lane < m && e.z == 0) == 0) {
       // ---- A: the repeat-offset history of the batch as a SCAN (lane i = sequence i). A sequence maps the history (r0, r1, r2) to a new
       // one whose components are each an old component (+ 0 or - 1) or a constant:
       //   j = 0: (r0, r1, r2)   1: (r1, r0, r2)   2: (r2, r0, r1)   3: (r0 - 1, r0, r1)   4, a new offset c: (c, r0, r1)
@@ -902,7 +824,6 @@ __device__ __forceinline__ uint32_t zq_consume(ZWave& w, const ZQueue& q, uint32
     for (uint32_t i = 0; i < m; ++i) {
       const uint32_t w0 = rdl(e.x, i), w1 = rdl(e.y, i), ov = rdl(e.z, i), w3 = rdl(e.w, i);
       if (ov) {                        // a sequence: w0 literals, then w1 bytes from an offset back
-        if (xmode & 1) continue;       // (experiments build only: xmode is 0 otherwise)
         // repeat offsets (RFC 8878 3.1.1.5) as selects on j = 0..3 (a repeat code, shifted by one when there are no literals) / 4
         // (a new offset): j = 0 offset r0, history unchanged; j = 1 r1, swapped to the front; j = 2 r2, j = 3 r0 - 1, j = 4 ov - 3
         uint32_t j = ov - 1 + (w0 == 0 ? 1u : 0u);

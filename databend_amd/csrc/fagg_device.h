@@ -94,12 +94,8 @@ __host__ __device__ constexpr int fa_blk_words(const FaArgs& M) { return fa_blk_
 #include "fagg_meta.inc"
 // Row slots per lane of the specialised kernel (its register file is per-lane VGPRs): chosen per shape by the host
 // (FA_META_ROWS, k_fagg.hip jit_rows: enough rows that a lane keeps >= 256 bytes in flight once every load of a chunk is issued
-// up front — 4 for Q1's 68-byte rows, 16 for a 16-byte key + argument row); -DFA_JIT_ROWS=n overrides (experiments).
-#if defined(FA_JIT_ROWS)
-constexpr int FA_ROWS = FA_JIT_ROWS;
-#else
+// up front — 4 for Q1's 68-byte rows, 16 for a 16-byte key + argument row).
 constexpr int FA_ROWS = FA_META_ROWS;
-#endif
 #define FA_LOOP_META _Pragma("unroll")
 #else
 #define FA_LOOP_META _Pragma("nounroll")

@@ -179,8 +179,8 @@ int32_t pin_string_states(dbhip_groupby* g, hipStream_t s) {
                      (uint64_t)g->arena + g->arena_cap, 4, na, (int64_t)0, g->ctrl, acc);
   DBHIP_LAUNCH_CHECK();
   DBHIP_CHECK(hipStreamSynchronize(s));
-  if (getenv("DBHIP_TRACE")) fprintf(stderr, "[dbhip] groupby: string arena compacted, %llu bytes in use -> %llu live (capacity %zu -> %zu)\n",
-                                     (unsigned long long)two[1], (unsigned long long)two[0], g->arena_cap, want);
+  trace("groupby: string arena compacted, %llu bytes in use -> %llu live (capacity %zu -> %zu)",
+        (unsigned long long)two[1], (unsigned long long)two[0], g->arena_cap, want);
   (void)dbhip_free(g->arena);
   g->arena = na;
   g->arena_cap = want;
@@ -232,8 +232,7 @@ int32_t merge_rows_unpinned(dbhip_groupby* g, const uint64_t* rows_in, int64_t n
   // the host reads the control block ONCE (the small merges behind the fused kernels are all host round trips).
   // (n is the caller's BOUND: one workgroup walks 256 rows per step at ~25 us a step — 2,048 partial rows behind dbhip_q1_fused took 240 us
   //  this way against 70 us through the three kernels, r06 probe — so only merges of at most one step take it)
-  static const int64_t small_n = exp_env("DBHIP_GB_SMALL_MERGE") ? atoll(exp_env("DBHIP_GB_SMALL_MERGE")) : 256;
-  if ((deferred || (g->count_host + n) * 135 <= g->cap * 100) && n <= small_n) {
+  if ((deferred || (g->count_host + n) * 135 <= g->cap * 100) && n <= 256) {
     // one launch of one workgroup instead of a memset and three kernels (gb_merge_small_kernel: such a merge is bound by the host's cost per
     // queued operation)
     hipLaunchKernelGGL(gb_merge_small_kernel, dim3(1), dim3(256), 0, s, g->L, cur_rows, cur_n, g->slot_hash, g->rows, g->cap, g->hash_mask, g->gid,

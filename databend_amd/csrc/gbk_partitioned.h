@@ -7,8 +7,7 @@ __device__ __forceinline__ uint32_t part_of(uint64_t h, int pbits) { return (uin
 #include "gb_compact.h"
 
 bool gbc_enabled(const dbhip_groupby* g) {
-  static const bool off = exp_env("DBHIP_GBC") && atoi(exp_env("DBHIP_GBC")) == 0;
-  return !off && !g->gbc_off && g->hash_mask == ~0ULL && !g->has_long;
+  return !g->gbc_off && g->hash_mask == ~0ULL && !g->has_long;
 }
 
 // the kernels are instantiated for 1-4 key words and 1 / 2 / 4 / 8 value words (a layout without value words runs as NV = 1)
@@ -56,9 +55,9 @@ void adapt_chunk(dbhip_groupby* g, int64_t n_block) {
   g->part_chunk = (int64_t)c;
   g->part_direct = D * 1.5 > (double)total ? 1 : 0;
   if (g->part_direct) g->part_chunk = PT_CHUNK;
-  if (getenv("DBHIP_TRACE")) fprintf(stderr, "[dbhip] groupby adaptive: %lld groups in %lld rows -> ~%lld groups, next chunk %lld rows%s\n",
-                                     (long long)g->count_host, (long long)g->rows_seen, (long long)est, (long long)g->part_chunk,
-                                     g->part_direct ? " (direct insert)" : "");
+  trace("groupby adaptive: %lld groups in %lld rows -> ~%lld groups, next chunk %lld rows%s",
+        (long long)g->count_host, (long long)g->rows_seen, (long long)est, (long long)g->part_chunk,
+        g->part_direct ? " (direct insert)" : "");
 }
 
 // one partitioned chunk starting at *done; widens the partitioning (or gives it up) when too many rows spilled
@@ -69,8 +68,8 @@ int32_t partitioned_step(dbhip_groupby* g, const GbCols& C, int64_t n, hipStream
   int32_t rc = add_chunk_partitioned(g, C, *done, cn, s, &spilled);
   if (rc) return rc;
   if (spilled < 0) { g->part_bits = -1; return DBHIP_OK; }   // long string keys: the caller's row path takes the rows from *done
-  if (getenv("DBHIP_TRACE")) fprintf(stderr, "[dbhip] groupby partitioned chunk: rows=%lld pbits=%d spilled=%lld groups=%lld\n",
-                                     (long long)cn, g->part_bits, (long long)spilled, (long long)g->count_host);
+  trace("groupby partitioned chunk: rows=%lld pbits=%d spilled=%lld groups=%lld",
+        (long long)cn, g->part_bits, (long long)spilled, (long long)g->count_host);
   *done += cn;
   g->rows_seen += cn;
   if (g->part_validate) {   // the check chunk of an extrapolated estimate: choose again with what it found
@@ -138,13 +137,12 @@ int32_t add_block_fast(dbhip_groupby* g, const GbCols& C, int64_t n, hipStream_t
     // Only the RUN-TIME SPECIALISED form of that kernel is used here (r02g: interpreted it loses to the LDS path, 1.34 vs 1.04 ms
     // per 60 M rows; specialised, with every load of a chunk issued up front, r03: see DESIGN §2.3). Plain add_block has no
     // PREPARE, so the kernel is looked up in the in-process / on-disk caches; when it is nowhere yet a detached helper compiles it
-    // into the on-disk cache and THIS block takes the LDS path — a query never waits for a compiler. DBHIP_FAGG_AUTO=0 disables.
-    static const bool fagg_auto_off = exp_env("DBHIP_FAGG_AUTO") && atoi(exp_env("DBHIP_FAGG_AUTO")) == 0;
+    // into the on-disk cache and THIS block takes the LDS path — a query never waits for a compiler.
     // A table that has not seen a row yet tries the kernel OPTIMISTICALLY, without the probing chunk, when the kernel already
     // exists (no compile is started for a shape whose cardinality is unknown): a workgroup that meets a 9th group stops at
     // once and nothing is merged, so a high-cardinality block loses a few microseconds and goes on to probe as before.
     const bool fresh = !g->fast_trusted && g->rows_seen == 0 && g->count_host == 0;
-    if (!fagg_auto_off && (g->fast_trusted || fresh) && !g->fagg_disabled && g->count_host <= 8 && n - *done >= (1 << 20)) {
+    if ((g->fast_trusted || fresh) && !g->fagg_disabled && g->count_host <= 8 && n - *done >= (1 << 20)) {
       rc = dbhip_fagg_add_columns_internal(g, C, *done, n - *done, /*may_compile=*/g->fast_trusted != 0, s);
       if (rc == DBHIP_OK) {
         g->rows_seen += n - *done;
@@ -168,7 +166,6 @@ int32_t add_block_fast(dbhip_groupby* g, const GbCols& C, int64_t n, hipStream_t
     if (probing) limit = 1 << 18;
     else if (g->fast_trusted) limit = n;
     const bool small = small_layout && !probing;
-    static const int small_r = exp_env("DBHIP_LDS_R") ? atoi(exp_env("DBHIP_LDS_R")) : 4;   // 4 (116 VGPRs, 4 waves / SIMD) or 8 (178, 2): r02n 1.00 vs 1.68 ms at 4 groups
     // BIG table (r03): a small layout whose groups outgrew the 48 KB table (768 groups of 4 words) but fit one twice the size
     // runs ONE 1024-thread workgroup per CU on a 96 KB table (the same 4 waves per SIMD) instead of going through the
     // partitioning passes — 1000 groups: 1.97 ms partitioned, see DESIGN §2.3
@@ -176,7 +173,8 @@ int32_t add_block_fast(dbhip_groupby* g, const GbCols& C, int64_t n, hipStream_t
     // compact kernel: ONE 1024-thread workgroup per CU, 4 rows per lane, a table sized for the groups the probing chunk predicted
     // (the largest table, gbc_max_lcap = 4096 slots / 112 KB for key + sum + count, while nothing is known)
     const int gbc_lcap = gbc ? (g->gbc_lcap ? g->gbc_lcap : gbc_max_lcap(GD)) : 0;   // (nothing known yet: the largest table)
-    const int R = gbc ? gbc_rows_per_lane(gbc_row_words(GD)) : (small ? ((small_r == 4 || big) ? 4 : 8) : 2);
+    // small layouts: 4 rows per lane (116 VGPRs, 4 waves / SIMD; 8 rows: 178 VGPRs, 2 waves — r02n 1.00 vs 1.68 ms at 4 groups)
+    const int R = gbc ? gbc_rows_per_lane(gbc_row_words(GD)) : (small ? 4 : 2);
     const int threads = (big || gbc) ? 1024 : 256;
     const int lcap_i = gbc ? gbc_lcap : (big ? lcap * 2 : lcap);
     const size_t lds_i = gbc ? gbc_agg_lds_bytes(GD, gbc_lcap, GBC_T) : (big ? lds_bytes * 2 : lds_bytes);
@@ -232,8 +230,7 @@ int32_t add_block_fast(dbhip_groupby* g, const GbCols& C, int64_t n, hipStream_t
       std::call_once(attr_once, [] { attr_err = hipFuncSetAttribute((const void*)gb_lds_preagg_kernel<2, 2, false, 4, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024); });
       DBHIP_CHECK(attr_err);
       hipLaunchKernelGGL((gb_lds_preagg_kernel<2, 2, false, 4, 1024>), dim3(grid), dim3(1024), lds_i, s, L, C, A);
-    } else if (small && R == 4) hipLaunchKernelGGL((gb_lds_preagg_kernel<2, 2, false, 4>), dim3(grid), dim3(256), lds_bytes, s, L, C, A);
-    else if (small) hipLaunchKernelGGL((gb_lds_preagg_kernel<2, 2, false, 8>), dim3(grid), dim3(256), lds_bytes, s, L, C, A);
+    } else if (small) hipLaunchKernelGGL((gb_lds_preagg_kernel<2, 2, false, 4>), dim3(grid), dim3(256), lds_bytes, s, L, C, A);
     else hipLaunchKernelGGL((gb_lds_preagg_kernel<FK_MAXKW, FK_MAXA, true, 2>), dim3(grid), dim3(256), lds_bytes, s, L, C, A);
     DBHIP_LAUNCH_CHECK();
     uint64_t hc[8];
@@ -272,8 +269,8 @@ int32_t add_block_fast(dbhip_groupby* g, const GbCols& C, int64_t n, hipStream_t
       const bool fits = (int64_t)want * 6 >= est * 10;
       if (fits && want != gbc_lcap) {
         g->gbc_lcap = want;
-        if (getenv("DBHIP_TRACE")) fprintf(stderr, "[dbhip] groupby: %lld groups in %lld rows -> ~%lld groups: compact LDS table of %d slots\n",
-                                           (long long)g->count_host, (long long)g->rows_seen, (long long)est, want);
+        trace("groupby: %lld groups in %lld rows -> ~%lld groups: compact LDS table of %d slots",
+              (long long)g->count_host, (long long)g->rows_seen, (long long)est, want);
       }
       if (fits) {
         g->fast_trusted = (int64_t)hc[6] * 100 <= cn || want > gbc_lcap;
@@ -283,19 +280,18 @@ int32_t add_block_fast(dbhip_groupby* g, const GbCols& C, int64_t n, hipStream_t
     if (((int64_t)hc[6] * 10 > cn || too_many) && cn >= 65536) {
       // twice the table is enough (estimated from the groups met so far): stay on the LDS path with the big table
       const int64_t big_limit = (int64_t)(lcap * 2 - lcap / 2) * 7 / 8;
-      static const bool big_off = exp_env("DBHIP_LDS_BIG") && atoi(exp_env("DBHIP_LDS_BIG")) == 0;
-      if (small_layout && !g->lds_big && !big_off && lds_bytes * 2 <= 128 * 1024 && estimate_groups(g->count_host, g->rows_seen) <= big_limit) {
+      if (small_layout && !g->lds_big && lds_bytes * 2 <= 128 * 1024 && estimate_groups(g->count_host, g->rows_seen) <= big_limit) {
         g->lds_big = 1;
         g->fast_trusted = 1;
-        if (getenv("DBHIP_TRACE")) fprintf(stderr, "[dbhip] groupby: %lld groups in %lld rows -> the 96 KB LDS table\n", (long long)g->count_host, (long long)g->rows_seen);
+        trace("groupby: %lld groups in %lld rows -> the 96 KB LDS table", (long long)g->count_host, (long long)g->rows_seen);
         continue;
       }
       g->lds_big = 0;
       decide_partitioning(g, g->count_host, g->rows_seen, n);
       if (g->part_bits < 0) g->fast_disabled = 1;
     }
-    if (getenv("DBHIP_TRACE")) fprintf(stderr, "[dbhip] groupby lds chunk: rows=%lld partial=%llu spilled=%llu groups=%lld -> pbits=%d\n",
-                                       (long long)cn, (unsigned long long)hc[5], (unsigned long long)hc[6], (long long)g->count_host, g->part_bits);
+    trace("groupby lds chunk: rows=%lld partial=%llu spilled=%llu groups=%lld -> pbits=%d",
+          (long long)cn, (unsigned long long)hc[5], (unsigned long long)hc[6], (long long)g->count_host, g->part_bits);
     g->fast_trusted = !too_many && (int64_t)hc[6] * 100 <= cn;
   }
   return DBHIP_OK;
@@ -1037,8 +1033,7 @@ int32_t gbc_partition_scatter(dbhip_groupby* g, const GbCols& C, const GbcDesc& 
   // 1024-thread workgroup per CU), one of 1024 threads beyond
   // (r04e: two 512-thread workgroups per CU instead of one of 1024 — 1024 row ranges instead of 512 — were SLOWER: 0.41 vs 0.38 ms at
   // 16 partitions, 0.69 vs 0.55 ms at 256: a workgroup's run inside a partition gets half as long)
-  static const int gbc_t = exp_env("DBHIP_GBC_T") ? atoi(exp_env("DBHIP_GBC_T")) : GBC_T;
-  const int T = (RW > 8 && P > 1024) ? 512 : gbc_t;   // (rows of 9 ... 12 words beside 16 K cursors: 512 staged rows fit the LDS)
+  const int T = (RW > 8 && P > 1024) ? 512 : GBC_T;   // (rows of 9 ... 12 words beside 16 K cursors: 512 staged rows fit the LDS)
   int64_t nwg = ceil_div(cn, (int64_t)T * 16);
   if (nwg > 512) nwg = 512;
   const int64_t rows_per_wg = ceil_div(cn, nwg);
@@ -1063,9 +1058,8 @@ int32_t gbc_partition_scatter(dbhip_groupby* g, const GbCols& C, const GbcDesc& 
   const int SR = RW <= 2 ? 4 : (RW <= 4 ? 2 : 1);
   // up to 1024 partitions: no histogram pass — fixed regions (the uniform share + 5 % + 16 K rows) and one global atomic per
   // (batch, partition); a region that overflows is found after the chunk's first read-back and the chunk redone the exact way
-  static const bool no_direct = exp_env("DBHIP_GBC_DIRECT") && atoi(exp_env("DBHIP_GBC_DIRECT")) == 0;
   g->gbc_part_cap = 0;
-  if (P <= 1024 && !g->gbc_nodirect && !no_direct && cn < ((int64_t)1 << 31)) {
+  if (P <= 1024 && !g->gbc_nodirect && cn < ((int64_t)1 << 31)) {
     // a partition's share of the rows follows its share of the GROUPS: with G groups spread over P partitions a partition holds
     // G / P +- sqrt(G / P) of them (10^4 groups, 16 partitions: +-4 % — r04h: a flat 5 % of slack overflowed there); five sigma + 5 %
     int64_t est = estimate_groups(g->count_host > 0 ? g->count_host : 1, g->rows_seen > 0 ? g->rows_seen : 1);
@@ -1119,8 +1113,7 @@ void part_geometry(const GbLayout& L, int* lcap, int* sw, size_t* lds_bytes) {
 // halving of the partition count (longer runs per workgroup and partition).
 int gbc_part_threads(int lcap) { return lcap >= 4096 ? 1024 : (lcap >= 2048 ? 512 : 256); }
 int gbc_part_lcap(const GbLayout& L, int lcap_max) {
-  static const int env_c = exp_env("DBHIP_GBC_PARTLCAP") ? atoi(exp_env("DBHIP_GBC_PARTLCAP")) : 0;   // (experiments)
-  const int max_c = env_c ? env_c : (lcap_max ? lcap_max : 2048);
+  const int max_c = lcap_max ? lcap_max : 2048;
   const size_t slot = (size_t)(L.nkey_words + (L.W - L.agg_off[0])) * 8 + 4;
   const size_t qrow = 48;   // (a deferred-row queue per wave: rows of up to 6 words, or the positions of wider rows)
   // two workgroups per CU (75 KB each) up to 2048 slots, one (150 KB) for 4096
@@ -1169,7 +1162,6 @@ int32_t partition_scatter(dbhip_groupby* g, const GbCols& C, int64_t row0, int64
   hipLaunchKernelGGL(gb_part_scan_kernel, dim3(1), dim3(1024), 0, s, tot, P, base);
   hipLaunchKernelGGL((gb_part_colscan_kernel<true>), dim3((P + 63) / 64), dim3(256), 0, s, mat, P, (int)nwg, tot, base);
   // staged copy-out while a batch of rows (2 or 1 per thread) fits the LDS beside the cursors; else lanes store their rows themselves
-  static const bool no_stage = exp_env("DBHIP_GB_NOSTAGE") != nullptr;
   const size_t row_bytes = 4 + (size_t)(L.W | 1) * 8;
   const size_t lds2 = (size_t)P * 4 + (size_t)T * 2 * row_bytes, lds1 = (size_t)P * 4 + (size_t)T * row_bytes;
   const size_t lds_max = 144 * 1024;
@@ -1180,10 +1172,10 @@ int32_t partition_scatter(dbhip_groupby* g, const GbCols& C, int64_t row0, int64
     if (raised_err == hipSuccess) raised_err = hipFuncSetAttribute((const void*)gb_part_scatter_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
   });
   DBHIP_CHECK(raised_err);
-  if (!no_stage && lds2 <= lds_max)
+  if (lds2 <= lds_max)
     hipLaunchKernelGGL((gb_part_scatter_kernel<2>), dim3((int)nwg), dim3(T), lds2, s, L, C, row0, cn, pbits, rows_per_wg, mat,
                        g->rows_in, g->ctrl);
-  else if (!no_stage && lds1 <= lds_max)
+  else if (lds1 <= lds_max)
     hipLaunchKernelGGL((gb_part_scatter_kernel<1>), dim3((int)nwg), dim3(T), lds1, s, L, C, row0, cn, pbits, rows_per_wg, mat,
                        g->rows_in, g->ctrl);
   else
@@ -1249,8 +1241,8 @@ int32_t add_chunk_partitioned(dbhip_groupby* g, const GbCols& C, int64_t row0, i
       DBHIP_LAUNCH_CHECK();
       if ((rc = merge_rows(g, g->spill_rows, nlist, s))) return rc;
     }
-    if (getenv("DBHIP_TRACE")) fprintf(stderr, "[dbhip] groupby partitioned insert: rows=%lld listed=%lld groups=%lld cap=%lld\n",
-                                       (long long)cn, (long long)nlist, (long long)g->count_host, (long long)g->cap);
+    trace("groupby partitioned insert: rows=%lld listed=%lld groups=%lld cap=%lld",
+          (long long)cn, (long long)nlist, (long long)g->count_host, (long long)g->cap);
     *spilled = 0;   // (listed rows are no sign of a partitioning that is too coarse)
     return DBHIP_OK;
   }
@@ -1271,8 +1263,7 @@ int32_t add_chunk_partitioned(dbhip_groupby* g, const GbCols& C, int64_t row0, i
   if ((rc = ensure((void**)&g->partial, &g->partial_cap, (size_t)agrid * lcap * L.W * 8))) return rc;
   // one workgroup per partition and a table at least as fine as the partitioning: the partial rows stay per partition and
   // are merged by the partition's own workgroup (gb_part_merge_kernel); otherwise one packed list for the row path
-  static const bool no_excl = exp_env("DBHIP_GB_NOEXCL") != nullptr;
-  const bool exclusive = splits == 1 && !no_excl && g->hash_mask == ~0ULL;
+  const bool exclusive = splits == 1 && g->hash_mask == ~0ULL;
   uint32_t* pcount = g->part_meta + 2 * PT_PMAX + 8;
   if (exclusive) DBHIP_CHECK(hipMemsetAsync(pcount, 0, (size_t)P * 4, s));
   DBHIP_CHECK(hipMemsetAsync(&g->ctrl[5], 0, 24, s));   // [5] partial rows, [6] spilled rows, [7] rows of the packed list of heavy partitions
@@ -1294,21 +1285,16 @@ int32_t add_chunk_partitioned(dbhip_groupby* g, const GbCols& C, int64_t row0, i
     // 10^6 where the partition has one workgroup): a partition longer than twice the average sub-range gets more sub-ranges, worked
     // on by EXTRA workgroups behind the regular P x splits (at most cn / max_rows of them; those not needed leave at once). Their
     // partial rows go to a packed list behind the per-partition lists and through the row path.
-    static const bool no_heavy = exp_env("DBHIP_GBC_HEAVY") && atoi(exp_env("DBHIP_GBC_HEAVY")) == 0;
-    int extra_max = 0;
-    if (!no_heavy) {
-      int64_t max_rows = 2 * (cn / agrid);
-      if (max_rows < 32768) max_rows = 32768;
-      extra_max = (int)(cn / max_rows) + 1;
-      if ((rc = ensure((void**)&g->gbc_split, &g->gbc_split_cap, ((size_t)P + 2 + (size_t)extra_max) * 4))) return rc;
-      if ((rc = ensure((void**)&g->partial, &g->partial_cap, ((size_t)agrid + 2 * (size_t)extra_max) * lcap * L.W * 8))) return rc;
-      G.partial = g->partial;
-      G.nsp = g->gbc_split; G.extra_n = g->gbc_split + P + 1; G.extra_map = g->gbc_split + P + 2;
-      G.nparts = P; G.packed_base = (uint64_t)agrid * lcap;
-      hipLaunchKernelGGL(gbc_split_map_kernel, dim3(1), dim3(1024), 0, s, G.pcursor, G.part_cap, base, P, splits, (uint32_t)max_rows, (uint32_t)extra_max, g->gbc_split);
-    }
-    static const int agg_t = exp_env("DBHIP_GBC_AGGT") ? atoi(exp_env("DBHIP_GBC_AGGT")) : 0;   // (experiments)
-    const int threads = agg_t ? agg_t : gbc_part_threads(lcap);
+    int64_t max_rows = 2 * (cn / agrid);
+    if (max_rows < 32768) max_rows = 32768;
+    const int extra_max = (int)(cn / max_rows) + 1;
+    if ((rc = ensure((void**)&g->gbc_split, &g->gbc_split_cap, ((size_t)P + 2 + (size_t)extra_max) * 4))) return rc;
+    if ((rc = ensure((void**)&g->partial, &g->partial_cap, ((size_t)agrid + 2 * (size_t)extra_max) * lcap * L.W * 8))) return rc;
+    G.partial = g->partial;
+    G.nsp = g->gbc_split; G.extra_n = g->gbc_split + P + 1; G.extra_map = g->gbc_split + P + 2;
+    G.nparts = P; G.packed_base = (uint64_t)agrid * lcap;
+    hipLaunchKernelGGL(gbc_split_map_kernel, dim3(1), dim3(1024), 0, s, G.pcursor, G.part_cap, base, P, splits, (uint32_t)max_rows, (uint32_t)extra_max, g->gbc_split);
+    const int threads = gbc_part_threads(lcap);
     lds_bytes = gbc_agg_lds_bytes(D, lcap, threads);
     static std::once_flag agg_raised_once;
     static hipError_t agg_raised_err = hipSuccess;
@@ -1323,19 +1309,15 @@ int32_t add_chunk_partitioned(dbhip_groupby* g, const GbCols& C, int64_t row0, i
 #undef GBC_AGG
   } else {
     // heavy partitions: the same split as for the compact kernels (the generic partitions are exact: base[], from the histogram pass)
-    static const bool no_heavy = exp_env("DBHIP_GBC_HEAVY") && atoi(exp_env("DBHIP_GBC_HEAVY")) == 0;
-    int extra_max = 0;
-    A.nsp = nullptr; A.extra_n = nullptr; A.extra_map = nullptr; A.nparts = P; A.packed_base = (uint64_t)agrid * lcap;
-    if (!no_heavy) {
-      int64_t max_rows = 2 * (cn / agrid);
-      if (max_rows < 32768) max_rows = 32768;
-      extra_max = (int)(cn / max_rows) + 1;
-      if ((rc = ensure((void**)&g->gbc_split, &g->gbc_split_cap, ((size_t)P + 2 + (size_t)extra_max) * 4))) return rc;
-      if ((rc = ensure((void**)&g->partial, &g->partial_cap, ((size_t)agrid + 2 * (size_t)extra_max) * lcap * L.W * 8))) return rc;
-      A.partial = g->partial;
-      A.nsp = g->gbc_split; A.extra_n = g->gbc_split + P + 1; A.extra_map = g->gbc_split + P + 2;
-      hipLaunchKernelGGL(gbc_split_map_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t*)nullptr, 0u, base, P, splits, (uint32_t)max_rows, (uint32_t)extra_max, g->gbc_split);
-    }
+    A.nparts = P; A.packed_base = (uint64_t)agrid * lcap;
+    int64_t max_rows = 2 * (cn / agrid);
+    if (max_rows < 32768) max_rows = 32768;
+    const int extra_max = (int)(cn / max_rows) + 1;
+    if ((rc = ensure((void**)&g->gbc_split, &g->gbc_split_cap, ((size_t)P + 2 + (size_t)extra_max) * 4))) return rc;
+    if ((rc = ensure((void**)&g->partial, &g->partial_cap, ((size_t)agrid + 2 * (size_t)extra_max) * lcap * L.W * 8))) return rc;
+    A.partial = g->partial;
+    A.nsp = g->gbc_split; A.extra_n = g->gbc_split + P + 1; A.extra_map = g->gbc_split + P + 2;
+    hipLaunchKernelGGL(gbc_split_map_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t*)nullptr, 0u, base, P, splits, (uint32_t)max_rows, (uint32_t)extra_max, g->gbc_split);
     if (L.W <= 8) hipLaunchKernelGGL((gb_part_agg_kernel<8>), dim3(agrid + extra_max), dim3(256), lds_bytes, s, L, A);
     else hipLaunchKernelGGL((gb_part_agg_kernel<0>), dim3(agrid + extra_max), dim3(256), lds_bytes, s, L, A);
   }
@@ -1355,7 +1337,7 @@ int32_t add_chunk_partitioned(dbhip_groupby* g, const GbCols& C, int64_t row0, i
     // redo it with the exact histogram
     DBHIP_CHECK(hipMemsetAsync(&g->ctrl[3], 0, 8, s));
     g->gbc_nodirect = 1;
-    if (getenv("DBHIP_TRACE")) fprintf(stderr, "[dbhip] groupby: a partition outgrew its region, chunk redone with the histogram pass\n");
+    trace("groupby: a partition outgrew its region, chunk redone with the histogram pass");
     return add_chunk_partitioned(g, C, row0, cn, s, spilled);
   }
   if (gbc && (hc[3] & 4)) {
@@ -1405,8 +1387,8 @@ int32_t add_chunk_partitioned(dbhip_groupby* g, const GbCols& C, int64_t row0, i
   if (ngather + nlisted > 0 && (rc = merge_rows(g, g->spill_rows, ngather + nlisted, s))) return rc;
   if (npacked > 0 && (rc = merge_rows(g, g->partial + (size_t)agrid * lcap * L.W, npacked, s))) return rc;
   if (gbc && nspill > 0 && (rc = merge_rows(g, g->gbc_spill, nspill, s))) return rc;
-  if (getenv("DBHIP_TRACE")) fprintf(stderr, "[dbhip] groupby partitioned merge: exclusive=%d partial=%lld listed=%lld spilled=%lld cap=%lld\n",
-                                     (int)exclusive, (long long)npartial, (long long)nlisted, (long long)nspill, (long long)g->cap);
+  trace("groupby partitioned merge: exclusive=%d partial=%lld listed=%lld spilled=%lld cap=%lld",
+        (int)exclusive, (long long)npartial, (long long)nlisted, (long long)nspill, (long long)g->cap);
   *spilled = nspill;
   return DBHIP_OK;
 }
@@ -1458,8 +1440,6 @@ void decide_partitioning(dbhip_groupby* g, int64_t groups, int64_t rows_seen, in
   if (((int64_t)per_part << bits) < est) {
     // more groups than the finest partitioning's LDS tables hold at once, or a probe that was (nearly) all distinct and
     // says nothing: finest partitioning, a 4 M-row chunk to learn from, then chunks sized by the estimate (adapt_chunk)
-    static const bool no_adapt = exp_env("DBHIP_GB_NODIRECT") != nullptr;
-    if (no_adapt) { g->part_bits = -1; return; }
     bits = PT_MAX_BITS;
     g->part_adapt = 1;
     g->part_chunk = 4 << 20;
@@ -1469,16 +1449,14 @@ void decide_partitioning(dbhip_groupby* g, int64_t groups, int64_t rows_seen, in
   // equally likely groups: one heavy key (25 % NULLs) made 10^6 groups look like 3 x 10^5 (r05), the partitioning came out four times
   // too coarse and 9 M of 60 M rows left the full tables for the row path (124 ms). Such an estimate is checked on a 4 M-row chunk
   // first; the partitioning of the rest follows what that chunk found (partitioned_step).
-  static const bool no_validate = exp_env("DBHIP_GB_VALIDATE") && atoi(exp_env("DBHIP_GB_VALIDATE")) == 0;
-  if (!g->part_adapt && !g->part_validated && !no_validate && groups * 4 > rows_seen && total - rows_seen > (16 << 20)) {
+  if (!g->part_adapt && !g->part_validated && groups * 4 > rows_seen && total - rows_seen > (16 << 20)) {
     g->part_validate = 1;
-    // (1 M rows by default, DBHIP_GB_VALIDATE_ROWS: at 10^6 groups under a 25 % heavy key they put the estimate within 1.3 x, which the
-    // tables' slack absorbs — a partition is sized for 3/8 of its table and spills at 3/4; 4 M rows cost the uniform 10^6 case 0.3 ms)
-    static const int64_t vrows = [] { const char* e = exp_env("DBHIP_GB_VALIDATE_ROWS"); const long long v = e ? atoll(e) : 0; return (int64_t)(v >= (1 << 18) ? v : (1 << 20)); }();
-    g->part_chunk = vrows;
+    // (1 M rows: at 10^6 groups under a 25 % heavy key they put the estimate within 1.3 x, which the tables' slack absorbs — a
+    // partition is sized for 3/8 of its table and spills at 3/4; 4 M rows cost the uniform 10^6 case 0.3 ms)
+    g->part_chunk = 1 << 20;
   }
-  if (getenv("DBHIP_TRACE")) fprintf(stderr, "[dbhip] groupby: %lld groups in the first %lld rows -> ~%lld groups in %lld rows, %d partition bits\n",
-                                     (long long)groups, (long long)rows_seen, (long long)est, (long long)total, bits);
+  trace("groupby: %lld groups in the first %lld rows -> ~%lld groups in %lld rows, %d partition bits",
+        (long long)groups, (long long)rows_seen, (long long)est, (long long)total, bits);
 }
 
 }  // namespace

@@ -553,7 +553,6 @@ int32_t dbhip_expr_eval(const dbhip_expr_ins* prog_host, int32_t n_ins, const db
     case DBHIP_T_DEC128: O.out_kind = 16; break;
     default: O.out_kind = type_bits(root.type) / 8; break;
   }
-  static const bool force2 = exp_env("DBHIP_EXPR_ROWS2") != nullptr;
   kernel_timer_start(s);
   // row slots per lane: 4 (32 B per operand per lane in flight, half the per-row interpreter overhead) while the LDS register
   // file allows it, else 2
@@ -561,7 +560,7 @@ int32_t dbhip_expr_eval(const dbhip_expr_ins* prog_host, int32_t n_ins, const db
   bool has_div = false;
   for (int i = 0; i < P.n_ins; ++i) has_div |= P.ins[i].op == EX_DEC && dec_op_needs_division(P.dec[P.ins[i].dec_idx]);
   int rows_per_lane = 2;
-  if (!force2 && !has_div && (size_t)P.n_slots * 4 * 256 * 8 <= 64 * 1024) rows_per_lane = 4;
+  if (!has_div && (size_t)P.n_slots * 4 * 256 * 8 <= 64 * 1024) rows_per_lane = 4;
   const size_t lds = (size_t)(P.n_slots > 0 ? P.n_slots : 1) * rows_per_lane * 256 * 8;
   if (lds > 64 * 1024) {
     set_error("dbhip_expr_eval: %d live registers exceed the LDS register file; split the expression", P.n_slots);

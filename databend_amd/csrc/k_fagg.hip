@@ -211,12 +211,12 @@ std::string jit_cache_dir() {
   if (const char* h = getenv("HOME")) if (*h) return std::string(h) + "/.cache/dbhip";
   return std::string();
 }
-std::string jit_cache_path(const std::string& meta, const std::string& tail, const std::string& arch, const std::string& defs) {
+std::string jit_cache_path(const std::string& meta, const std::string& tail, const std::string& arch) {
   const std::string dir = jit_cache_dir();
   if (dir.empty()) return dir;
   uint64_t h1 = 0xcbf29ce484222325ULL, h2 = 0x84222325cbf29ce4ULL;
   auto mix = [&](const void* d, size_t n) { h1 = fnv1a(d, n, h1); h2 = fnv1a(d, n, h2 ^ 0x9e3779b97f4a7c15ULL); };
-  mix(meta.data(), meta.size()); mix(tail.data(), tail.size()); mix(arch.data(), arch.size()); mix(defs.data(), defs.size());
+  mix(meta.data(), meta.size()); mix(tail.data(), tail.size()); mix(arch.data(), arch.size());
   for (int i = 0; i < kJitHdrCount; ++i) mix(kJitHdrSrc[i], strlen(kJitHdrSrc[i]));
   char name[64];
   snprintf(name, sizeof(name), "/fagg_%016llx%016llx.co", (unsigned long long)h1, (unsigned long long)h2);
@@ -284,8 +284,7 @@ void mkdir_p(const std::string& dir) {
 // sources lives inside it, so that the helper's rename stays on one file system).
 bool jit_compile(const std::string& meta, const std::string& tail, std::vector<char>* code, std::string* log, bool detached = false) {
   const std::string arch = jit_arch();
-  const std::string defs = exp_env("DBHIP_FAGG_JIT_DEFS") ? exp_env("DBHIP_FAGG_JIT_DEFS") : "";
-  const std::string cached = jit_cache_path(meta, tail, arch, defs);
+  const std::string cached = jit_cache_path(meta, tail, arch);
   if (!cached.empty() && read_cached_code(cached, code)) return true;   // compiled by an earlier process (or an earlier table)
   code->clear();
   const std::string helper = jit_helper_path();
@@ -313,13 +312,6 @@ bool jit_compile(const std::string& meta, const std::string& tail, std::vector<c
   if (detached) { args.push_back("--detach"); args.push_back("--publish"); args.push_back(cached); args.push_back("--rmdir"); args.push_back(dir); }
   for (const std::string& a : {dir + "/main.hip", dir + "/out.co", "-I" + dir, "--offload-arch=" + arch, std::string("-O3"), std::string("-std=c++17"),
                                std::string("-mllvm"), std::string("-pragma-unroll-threshold=4000000")}) args.push_back(a);
-  if (const char* e = exp_env("DBHIP_FAGG_JIT_DEFS")) {   // experiment knobs, e.g. "-DFA_JIT_ROWS=4 -DFA_JIT_GLOBAL" (read per compile)
-    std::string t;
-    for (const char* c = e;; ++c) {
-      if (*c == ' ' || *c == 0) { if (!t.empty()) args.push_back(t); t.clear(); if (!*c) break; }
-      else t.push_back(*c);
-    }
-  }
   std::vector<char*> argv;
   for (std::string& a : args) argv.push_back(&a[0]);
   argv.push_back(nullptr);
@@ -428,7 +420,7 @@ hipFunction_t jit_kernel(const FaArgs& A, int slots, bool general, int nw, int h
   if (mode == 0) return nullptr;
   if (mode == 2) how = JIT_COMPILE;
   // in-process key: the binary image of the query shape (FaArgs with everything that varies between calls of one shape
-  // zeroed — the fields jit_meta prints as null / 0), the variant, the experiment knobs and the device the module is loaded
+  // zeroed — the fields jit_meta prints as null / 0), the variant and the device the module is loaded
   // on. (Generating the metadata TEXT per call to look the kernel up cost 0.25 ms of host time per launch.)
   FaArgs K;
   fa_shape(A, K);
@@ -436,8 +428,6 @@ hipFunction_t jit_kernel(const FaArgs& A, int slots, bool general, int nw, int h
   (void)hipGetDevice(&dev);
   std::string key((const char*)&K, sizeof(K));
   key += "|" + std::to_string(slots) + "|" + std::to_string((int)general) + "|" + std::to_string(nw) + "|" + std::to_string(dev) + "|" + (multi ? "m|" : "|");
-  key += exp_env("DBHIP_FAGG_JIT_DEFS") ? exp_env("DBHIP_FAGG_JIT_DEFS") : "";
-  const bool trace = getenv("DBHIP_TRACE") != nullptr;
   std::lock_guard<std::mutex> lock(g_jit_mu);
   auto it = g_jit_cache.find(key);
   const auto now = std::chrono::steady_clock::now();
@@ -457,7 +447,7 @@ hipFunction_t jit_kernel(const FaArgs& A, int slots, bool general, int nw, int h
   std::string log;
   bool have = false;
   {
-    const std::string cached = jit_cache_path(meta, tail, jit_arch(), exp_env("DBHIP_FAGG_JIT_DEFS") ? exp_env("DBHIP_FAGG_JIT_DEFS") : "");
+    const std::string cached = jit_cache_path(meta, tail, jit_arch());
     have = !cached.empty() && read_cached_code(cached, &code);
   }
   const bool from_disk = have;
@@ -465,45 +455,37 @@ hipFunction_t jit_kernel(const FaArgs& A, int slots, bool general, int nw, int h
     have = jit_compile(meta, tail, &code, &log);
     if (!have) {
       e.state = JitEntry::FAILED;
-      if (trace) fprintf(stderr, "[dbhip] fagg jit: hiprtc failed; the interpreting kernel is used.\n%s\n", log.c_str());
+      trace("fagg jit: hiprtc failed; the interpreting kernel is used.\n%s", log.c_str());
       return nullptr;
     }
   }
   if (!have && how == JIT_BACKGROUND && e.state != JitEntry::PENDING) {
     code.clear();
     (void)jit_compile(meta, tail, &code, &log, true);
-    if (log == "pending") { e.state = JitEntry::PENDING; e.started = now; if (trace) fprintf(stderr, "[dbhip] fagg jit: compiling in the background\n"); }
-    else { e.state = JitEntry::FAILED; if (trace) fprintf(stderr, "[dbhip] fagg jit: no background compile: %s\n", log.c_str()); }
+    if (log == "pending") { e.state = JitEntry::PENDING; e.started = now; trace("fagg jit: compiling in the background"); }
+    else { e.state = JitEntry::FAILED; trace("fagg jit: no background compile: %s", log.c_str()); }
   }
   if (!have) {
     if (e.state == JitEntry::PENDING && now - e.started > std::chrono::seconds(120)) e.state = JitEntry::FAILED;   // the helper died
     if (pending) *pending = e.state == JitEntry::PENDING;
     return nullptr;
   }
-  if (const char* dump = exp_env("DBHIP_FAGG_JIT_DUMP")) {   // code object (and the generated metadata) for offline disassembly
-    static int seq = 0;
-    char path[512];
-    snprintf(path, sizeof(path), "%s.%d.co", dump, seq);
-    if (FILE* f = fopen(path, "wb")) { fwrite(code.data(), 1, code.size(), f); fclose(f); }
-    snprintf(path, sizeof(path), "%s.%d.meta", dump, seq++);
-    if (FILE* f = fopen(path, "wb")) { fwrite(meta.data(), 1, meta.size(), f); fwrite(tail.data(), 1, tail.size(), f); fclose(f); }
-  }
   if (hipModuleLoadData(&e.mod, code.data()) == hipSuccess && hipModuleGetFunction(&e.fn, e.mod, "fagg_jit") == hipSuccess) {
     e.state = JitEntry::READY;
-    if (trace) fprintf(stderr, "[dbhip] fagg jit: specialised kernel ready (%zu bytes of code)\n", code.size());
+    trace("fagg jit: specialised kernel ready (%zu bytes of code)", code.size());
     return e.fn;
   }
   if (from_disk) {
     // a cached file that does not load (another compiler's, corrupt): a cache miss, not a verdict on the shape — drop it so
     // that the next PREPARE / background compile writes a fresh one
-    const std::string cached = jit_cache_path(meta, tail, jit_arch(), exp_env("DBHIP_FAGG_JIT_DEFS") ? exp_env("DBHIP_FAGG_JIT_DEFS") : "");
+    const std::string cached = jit_cache_path(meta, tail, jit_arch());
     if (!cached.empty()) (void)unlink(cached.c_str());
     e.state = JitEntry::ABSENT;
-    if (trace) fprintf(stderr, "[dbhip] fagg jit: the cached code object did not load; removed, the shape will be compiled again\n");
+    trace("fagg jit: the cached code object did not load; removed, the shape will be compiled again");
     return nullptr;
   }
   e.state = JitEntry::FAILED;
-  if (trace) fprintf(stderr, "[dbhip] fagg jit: the code object did not load; the interpreting kernel is used\n");
+  trace("fagg jit: the code object did not load; the interpreting kernel is used");
   return nullptr;
 }
 
@@ -693,7 +675,6 @@ constexpr int FA_PIPE_WINDOW = 2048;  // blocks per window at most (one merge; w
                                       // fill the row buffer (16 launches of the full grid)
 constexpr int FA_PIPE_BATCH = 512;    // blocks per multi-block launch (r06 sweeps at 65,536-row blocks, one thread: 32 -> 25, 64 -> 33, 128 -> 40-43 G rows/s;
                                       // a launch costs ~40 us whatever it holds: 8 Mi rows per launch stream at 54 G rows/s, 32 Mi at 70+)
-constexpr int FA_PIPE_BATCH_MAX = 512; // (DBHIP_FAGG_PIPE_BATCH sweeps 2..512: experiments build)
 constexpr size_t FA_PIPE_COPY_BYTES = 16384;    // a pinned -> device hipMemcpyAsync above 16 KB blocks the calling thread on this stack (fagg_device.h,
                                                 // tools/probes/h2d_small_copy.hip): a launch's packed block table is uploaded in pieces of this size
 constexpr size_t FA_PIPE_TABLE_BYTES = 65536;   // one launch's packed block table (512 blocks of 16 words; wide shapes get fewer blocks per launch)
@@ -901,8 +882,7 @@ int32_t fa_pipe_flush_batch(dbhip_groupby* g, FaPipe* pp) {
 
 // a block enters a pipelined table: large ones are launched at once, small ones wait for company
 int32_t fa_pipe_enqueue(dbhip_groupby* g, FaPipe* pp, const FaPending& P, hipStream_t s) {
-  static const bool no_batch = exp_env("DBHIP_FAGG_PIPE_BATCH") && atoi(exp_env("DBHIP_FAGG_PIPE_BATCH")) == 0;
-  if (P.b.n >= FA_PIPE_BIG || no_batch || jit_mode() == 0) {
+  if (P.b.n >= FA_PIPE_BIG || jit_mode() == 0) {
     const int32_t rc = fa_pipe_flush_batch(g, pp);   // (blocks stay in call order)
     return rc ? rc : fa_pipe_submit(g, pp, P, s);
   }
@@ -912,9 +892,8 @@ int32_t fa_pipe_enqueue(dbhip_groupby* g, FaPipe* pp, const FaPending& P, hipStr
   }
   pp->batch.push_back(P);
   pp->batch_rows += P.b.n;
-  static const int batch_n = [] { const char* e = exp_env("DBHIP_FAGG_PIPE_BATCH"); const int v = e ? atoi(e) : 0; return v >= 2 && v <= FA_PIPE_BATCH_MAX ? v : FA_PIPE_BATCH; }();
   const int fit = (int)(FA_PIPE_TABLE_BYTES / ((size_t)fa_blk_words(pp->shapes[(size_t)P.shape].A) * 8));   // >= 210: a block is at most 39 words
-  if ((int)pp->batch.size() >= (batch_n < fit ? batch_n : fit) || pp->batch_rows >= FA_PIPE_BATCH_ROWS) return fa_pipe_flush_batch(g, pp);
+  if ((int)pp->batch.size() >= (FA_PIPE_BATCH < fit ? FA_PIPE_BATCH : fit) || pp->batch_rows >= FA_PIPE_BATCH_ROWS) return fa_pipe_flush_batch(g, pp);
   return DBHIP_OK;
 }
 
@@ -1098,9 +1077,7 @@ int32_t dbhip_groupby_add_block_program(dbhip_groupby* g, const dbhip_col* keys,
   }
   // grid: whole multiples of the 256 CUs, 2 workgroups per CU (k_q1.hip's sweep: fewer, longer-running workgroups stream best)
   const int64_t nchunks = ceil_div(n, 64 * FA_ROWS);
-  int grid = (int)(ceil_div(nchunks, 4) < 512 ? ceil_div(nchunks, 4) : 512);
-  static const int env_grid = exp_env("DBHIP_FAGG_GRID") ? atoi(exp_env("DBHIP_FAGG_GRID")) : 0;
-  if (env_grid > 0) grid = (int)(ceil_div(nchunks, 4) < env_grid ? ceil_div(nchunks, 4) : env_grid);
+  const int grid = (int)(ceil_div(nchunks, 4) < 512 ? ceil_div(nchunks, 4) : 512);
   if (FaPipe* pp = (FaPipe*)*dbhip_groupby_pipe_slot_internal(g); pp && !t_prepare_only) {
     int64_t committed = 0;         // a synchronous call on a table that still has queued blocks: those first
     if ((rc = fa_pipe_checkpoint(g, pp, &committed, true))) return rc;
@@ -1119,7 +1096,6 @@ int32_t dbhip_groupby_add_block_program(dbhip_groupby* g, const dbhip_col* keys,
   const int64_t n_max = (int64_t)grid * FA_MAX_SLOTS;
   const bool chained = (dbhip_groupby_count_internal(g) + n_max) * 135 <= dbhip_groupby_capacity_internal(g) * 100;
   if ((rc = dbhip_groupby_reserve_merge_internal(g, n_max))) return rc;
-  static const bool no_chain = exp_env("DBHIP_FAGG_NOCHAIN") != nullptr;   // debugging: drain the stream between kernel and merge
   if (t_prepare_only) {
     // dbhip_groupby_prepare_program: compile the specialised kernel of this query shape now (the 4-slot variant, or the
     // 8-slot one when the table already holds more than 4 groups), launch nothing
@@ -1138,7 +1114,7 @@ int32_t dbhip_groupby_add_block_program(dbhip_groupby* g, const dbhip_col* keys,
     kernel_timer_stop(s);
     DBHIP_LAUNCH_CHECK();
     DBHIP_CHECK(hipMemcpyAsync(host_ctrl, ctrl, 24, hipMemcpyDeviceToHost, s));
-    if (chained && !may_raise && !no_chain) {
+    if (chained && !may_raise) {
       // the merge of the partial rows is queued right behind the kernel with the row count and the give-up flags still
       // on the device: ONE host round trip per pass
       rc = dbhip_groupby_merge_rows_dev_internal(g, A.partial_rows, n_max, &ctrl[0], &ctrl[1], s);

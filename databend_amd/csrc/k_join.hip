@@ -86,18 +86,16 @@ __global__ __launch_bounds__(256) void join_copy_kernel(const uint64_t* keys, co
 // of independent runs — the same occupancy statistics as hashing every key on its own). r03, SF100 lineitem probe, 600 M rows:
 // 2.9 -> see DESIGN.md.
 template <int KW>
-__device__ __forceinline__ uint64_t join_bucket(const uint64_t* k, int cfg, uint32_t* tag) {
-  const int shift = cfg & 255;   // cfg = shift | D << 8
+__device__ __forceinline__ uint64_t join_bucket(const uint64_t* k, int shift, uint32_t* tag) {
   if (KW == 1) {
-    const int D = cfg >> 8;      // 2^D neighbouring key values share a bucket (sparse clustered keys, see dbhip_join_finalize)
     // (round 6) ONE multiply: Fibonacci hashing of the run id — the bucket index below takes the TOP bits of the product, the ones a
     // multiplicative hash mixes best; the table's geometry is private to this file (set-equal results). (Also tried in round 6
     // and reverted: an occupancy filter of 16 positions per build row instead of one bit per bucket — 12 % instead of 39 % of the probes
     // of a selective join go on to fetch a head sector, but the filter (29 MB for TPC-H Q3's orders) no longer stays in one XCD's L2:
     // Q3 SF100 9.46 -> 10.22 ms.)
-    const uint64_t hg = (k[0] >> (6 + D)) * 0x9E3779B97F4A7C15ULL;
+    const uint64_t hg = (k[0] >> 6) * 0x9E3779B97F4A7C15ULL;
     *tag = (uint32_t)((hg >> 40) ^ k[0]) & 15u;
-    return ((hg >> shift) + ((k[0] >> D) & 63u)) & ((~0ULL) >> shift);
+    return ((hg >> shift) + (k[0] & 63u)) & ((~0ULL) >> shift);
   }
   const uint64_t h = join_hash<KW>(k);
   *tag = (uint32_t)h & 15u;
@@ -686,7 +684,6 @@ int32_t dbhip_join_finalize(dbhip_join* j, void* stream) {
   while (cap < j->nrows * 2) cap <<= 1;  // hashjoin_hashtable.rs:95-108
   j->buckets = cap;
   j->shift = 64 - __builtin_ctzll((unsigned long long)cap);
-  if (j->kw == 1 && exp_env("DBHIP_JOIN_D")) j->shift |= atoi(exp_env("DBHIP_JOIN_D")) << 8;
   DBHIP_TRY(dbhip_alloc((size_t)cap * 8, (void**)&j->head));
   DBHIP_CHECK(hipMemsetAsync(j->head, 0, (size_t)cap * 8, s));
   if (j->nrows) {
@@ -697,9 +694,8 @@ int32_t dbhip_join_finalize(dbhip_join* j, void* stream) {
     else
       hipLaunchKernelGGL(join_build_kernel<4>, dim3(grid_for(j->nrows, 256)), dim3(256), 0, s, j->ent, j->nrows, j->head, j->shift);
     DBHIP_LAUNCH_CHECK();
-    // JOIN_OCC_MIN_BUCKETS: 2^20 heads = 8 MB, past what one XCD's L2 keeps; DBHIP_JOIN_OCC=0 turns the filter off (measurements)
-    static const bool occ_on = !(exp_env("DBHIP_JOIN_OCC") && exp_env("DBHIP_JOIN_OCC")[0] == '0');
-    if (occ_on && cap >= (1 << 20)) {
+    // JOIN_OCC_MIN_BUCKETS: 2^20 heads = 8 MB, past what one XCD's L2 keeps
+    if (cap >= (1 << 20)) {
       DBHIP_TRY(dbhip_alloc((size_t)cap / 8, (void**)&j->occ));
       hipLaunchKernelGGL(join_occ_kernel, dim3(grid_for(cap, 256)), dim3(256), 0, s, j->head, cap, j->occ);
       DBHIP_LAUNCH_CHECK();

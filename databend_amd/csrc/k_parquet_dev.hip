@@ -22,9 +22,9 @@
 //   pq_popc / scan / pq_spread (pq_common.h)   nullable columns: dense values -> rows.
 // Nothing is validated on the host beyond the page table, so every device access is checked against the page payload, the
 // dictionary and the output size; the first violation is recorded in a device word and decode returns DBHIP_ERR_INVALID.
-//   dv_inflate_zstd_kernel   ZSTD (the reference's DEFAULT codec, table_compression.rs:27-28): one wave per page walks the frame with
-//                       zstd_core.h (Huffman literals by up to four lanes, FSE sequences from a look-ahead window in registers, an 8 KiB
-//                       LDS ring + far references from the image: dv_wave.h).
+//   dv_inflate_zstd2_kernel  ZSTD (the reference's DEFAULT codec, table_compression.rs:27-28): two waves per page — one walks the frame
+//                       with zstd_core.h (Huffman literals by up to four lanes, FSE sequences from a look-ahead window in registers) and
+//                       queues commands, the other replays them through a 4 KiB LDS ring + far references from the image: dv_wave.h.
 // dbhip_pq_chunks_decode_device decodes MANY chunks with one launch set (one inflate launch per codec family over all their pages, one
 // levels / scan / dictionary / values launch over all their data pages, one read-back): a scan keeps dozens of column chunks in flight.
 #include "pq_common.h"
@@ -43,28 +43,8 @@ __device__ __forceinline__ void dv_fail(uint32_t* ctl, uint32_t code) { atomicCA
 __device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 
 // ---------------------------------------------------------------------------------------------
-// page decompression: one wave per page (dv_wave.h)
+// page decompression (dv_wave.h)
 // ---------------------------------------------------------------------------------------------
-// ZSTD: one wave per page (dv_wave.h, zstd_core.h) — the round-5 form, kept for A/B runs in the experiments build only (DBHIP_PQ_ZSTD_WAVES=1):
-// the shipped library always takes the two-wave kernel below
-#ifdef DBHIP_EXPERIMENTS
-__global__ __launch_bounds__(64) void dv_inflate_zstd_kernel(const DvJob* __restrict__ jobs, uint32_t ring) {
-  extern __shared__ __align__(16) uint8_t dv_lds[];
-  const DvJob P = jobs[blockIdx.x];
-  const uint32_t lane = threadIdx.x;
-  const uint32_t lev = P.lev_len;
-  const uint32_t raw = P.compressed ? lev : P.uncomp_len;
-  for (uint32_t i = lane; i < raw; i += 64) P.dst[i] = P.src[i];
-  if (!P.compressed || P.uncomp_len == lev) return;
-  ZWave w;
-  w.begin(P, dv_lds, ring, lane);
-  int rc = zc::decode_frames(w, w.in_len);
-  if (rc == zc::OK && w.op_ != w.cap_) rc = zc::CORRUPT_;
-  w.flush(true);
-  if (rc) dv_fail(P.ctl, rc == zc::UNSUPPORTED ? DV_UNSUPPORTED : DV_CORRUPT);
-}
-#endif
-
 // ZSTD, two waves per page: wave 0 parses (ZProd), wave 1 copies (dv_wave.h)
 __global__ __launch_bounds__(128) void dv_inflate_zstd2_kernel(const DvJob* __restrict__ jobs, uint32_t ring) {
   extern __shared__ __align__(16) uint8_t dv_lds[];
@@ -74,12 +54,6 @@ __global__ __launch_bounds__(128) void dv_inflate_zstd2_kernel(const DvJob* __re
   const uint32_t raw = P.compressed ? lev : P.uncomp_len;
   for (uint32_t i = threadIdx.x; i < raw; i += 128) P.dst[i] = P.src[i];
   if (!P.compressed || P.uncomp_len == lev) return;
-#ifdef DBHIP_EXPERIMENTS
-  const uint32_t xmode = ring >> 24;   // DBHIP_PQ_ZSTD_X: 1 = the consumer drains the queue without executing (wrong output on purpose)
-  ring &= 0xFFFFFFu;
-#else
-  const uint32_t xmode = 0;
-#endif
   ZQueue Q;
   Q.slots = (u32x4q*)(dv_lds + ring + ZW_TABLES);
   Q.ctl = (uint32_t*)(dv_lds + ring + ZW_TABLES + ZQ_CAP * 16);
@@ -89,30 +63,13 @@ __global__ __launch_bounds__(128) void dv_inflate_zstd2_kernel(const DvJob* __re
     ZProd a;
     a.begin(P, dv_lds, ring, lane);
     a.qbegin(Q);
-#ifdef DBHIP_EXPERIMENTS
-    const uint64_t x_t0 = __builtin_readcyclecounter();
-#endif
     int rc = zc::decode_frames(a, a.in_len);
     if (rc == zc::OK && a.op_ != a.cap_) rc = zc::CORRUPT_;
     a.end((uint32_t)rc);
-#ifdef DBHIP_EXPERIMENTS
-    if ((xmode & 32) && blockIdx.x < 4 && lane == 0)
-      printf("zstd2 page %u (%u -> %u bytes): producer %llu cycles, of which waiting for the consumer %llu\n", blockIdx.x, P.comp_len, P.uncomp_len,
-             (unsigned long long)(__builtin_readcyclecounter() - x_t0), (unsigned long long)a.x_wait);
-#endif
   } else {
     ZWave b;
     b.begin(P, dv_lds, ring, lane);
-#ifdef DBHIP_EXPERIMENTS
-    const uint64_t x_t0 = __builtin_readcyclecounter();
-    uint64_t x_cw[3] = {0, 0, 0};
-    const int rc = (int)zq_consume(b, Q, xmode, x_cw);
-    if ((xmode & 32) && blockIdx.x < 4 && lane == 0)
-      printf("zstd2 page %u: consumer %llu cycles, of which waiting for commands %llu; %llu sequences in straight batches, flushes in front of them %llu cycles\n", blockIdx.x,
-             (unsigned long long)(__builtin_readcyclecounter() - x_t0), (unsigned long long)x_cw[0], (unsigned long long)x_cw[1], (unsigned long long)x_cw[2]);
-#else
-    const int rc = (int)zq_consume(b, Q, xmode);
-#endif
+    const int rc = (int)zq_consume(b, Q);
     b.flush(true);
     if (rc) dv_fail(P.ctl, rc == zc::UNSUPPORTED ? DV_UNSUPPORTED : DV_CORRUPT);
   }
@@ -965,14 +922,6 @@ int32_t dbhip_pq_chunk_open_device_list(const uint8_t* chunk_host, int64_t chunk
 // ---- the batch: one launch set for many chunks ------------------------------------------------------------------------------
 namespace {
 
-uint32_t ring_from_env(const char* name, uint32_t dflt) {
-  const char* e = exp_env(name);   // (DBHIP_PQ_LZ_RING / DBHIP_PQ_ZSTD_RING: sweep knobs, experiments build only)
-  if (!e) return dflt;
-  const long v = atol(e);
-  if (v < 1024 || v > 65536 || (v & (v - 1))) return dflt;
-  return (uint32_t)v;
-}
-
 struct BlobLayout {
   size_t hdr, cds, dict_list, lv_map, val_map, jobs, per_chunk, total;
 };
@@ -1019,9 +968,6 @@ int32_t decode_many(dbhip_pq_chunk* const* cs, int32_t n, const uint8_t* const* 
   if (live.empty()) return DBHIP_OK;
   static const bool lds_ok = [] {
     return hipFuncSetAttribute((const void*)dv_inflate_lz_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LZ_RING) == hipSuccess &&
-#ifdef DBHIP_EXPERIMENTS
-           hipFuncSetAttribute((const void*)dv_inflate_zstd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ZW_LDS) == hipSuccess &&
-#endif
            hipFuncSetAttribute((const void*)dv_inflate_zstd2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ZW2_LDS) == hipSuccess;
   }();
   if (!lds_ok) { set_error("%s: cannot reserve LDS for the decompression kernels", who); return DBHIP_ERR_HIP; }
@@ -1130,20 +1076,10 @@ int32_t decode_many(dbhip_pq_chunk* const* cs, int32_t n, const uint8_t* const* 
       DBHIP_CHECK(hipMemsetAsync(spread ? c->d_dense : out_values_dev[i], 0, (size_t)ceil_div(spread ? c->rows + 1 : c->rows, 64) * 8, s));
   }
   kernel_timer_start(s);
-  // ring sizes (powers of two >= 1 KiB; env overrides for experiments): smaller rings = more pages resident per CU, more back-references
-  // served from the image instead of the ring
-  static const uint32_t z_ring = ring_from_env("DBHIP_PQ_ZSTD_RING", ZW_RING), lz_ring = ring_from_env("DBHIP_PQ_LZ_RING", LZ_RING);
-  // (two waves per page — parse | copy — unless DBHIP_PQ_ZSTD_WAVES=1 asks for the one-wave kernel)
-#ifdef DBHIP_EXPERIMENTS
-  static const bool z_one_wave = exp_env("DBHIP_PQ_ZSTD_WAVES") && atoi(exp_env("DBHIP_PQ_ZSTD_WAVES")) == 1;
-  if (n_z && z_one_wave) hipLaunchKernelGGL(dv_inflate_zstd_kernel, dim3((unsigned)n_z), dim3(64), z_ring + ZW_TABLES, s, d_jobs, z_ring);
-  else
-#endif
-  if (n_z) {
-    static const uint32_t z_x = exp_env("DBHIP_PQ_ZSTD_X") ? (uint32_t)atoi(exp_env("DBHIP_PQ_ZSTD_X")) << 24 : 0u;
-    hipLaunchKernelGGL(dv_inflate_zstd2_kernel, dim3((unsigned)n_z), dim3(128), z_ring + ZW_TABLES + ZQ_BYTES, s, d_jobs, z_ring | z_x);
-  }
-  if (n_jobs > n_z) hipLaunchKernelGGL(dv_inflate_lz_kernel, dim3((unsigned)(n_jobs - n_z)), dim3(64), lz_ring, s, d_jobs + n_z, lz_ring);
+  // ring sizes (dv_wave.h): smaller rings = more pages resident per CU, more back-references served from the image instead of the ring.
+  // ZSTD: two waves per page — parse | copy
+  if (n_z) hipLaunchKernelGGL(dv_inflate_zstd2_kernel, dim3((unsigned)n_z), dim3(128), ZW2_LDS, s, d_jobs, ZW_RING);
+  if (n_jobs > n_z) hipLaunchKernelGGL(dv_inflate_lz_kernel, dim3((unsigned)(n_jobs - n_z)), dim3(64), LZ_RING, s, d_jobs + n_z, LZ_RING);
   if (n_dict) hipLaunchKernelGGL(dv_dict_kernel, dim3((unsigned)n_dict), dim3(256), 0, s, d_cds, (const uint32_t*)(blob + L.dict_list));
   if (n_lv) hipLaunchKernelGGL(dv_levels_kernel, dim3((unsigned)n_lv), dim3(256), any_list ? LV_LDS : 0u, s, d_cds, (const uint2*)(blob + L.lv_map), any_list ? LV_LDS : 0u);
   hipLaunchKernelGGL(dv_scan_kernel, dim3((unsigned)nl), dim3(256), 0, s, d_cds);

@@ -947,16 +947,13 @@ int32_t dbhip_sort_perm(const dbhip_col* keys, const uint8_t* desc_host, const u
     }
   }
 
-  // 8192-key tiles of 512 threads (DBHIP_SORT_NT=256: the 4096-key tiles of rounds 1-3)
-  static const int rs_nt = exp_env("DBHIP_SORT_NT") ? atoi(exp_env("DBHIP_SORT_NT")) : 512;
-  const bool big_tiles = rs_nt == 512;
-  const int64_t ntiles = ceil_div(m, big_tiles ? 512 * SORT_ITEMS : SORT_TILE);
+  // 8192-key tiles of 512 threads
+  const int64_t ntiles = ceil_div(m, 512 * SORT_ITEMS);
   const int64_t nh = 256 * ntiles;
   // `final_vals`: this call holds the LAST pass of the whole sort — its permutation goes straight to the caller's buffer
   bool wrote_final = false;
-  // onesweep (above) for sorts of 2^20 rows and more in 8192-key tiles; DBHIP_SORT_ONESWEEP=0: the histogram / scan / scatter passes
-  static const bool onesweep_off = exp_env("DBHIP_SORT_ONESWEEP") && atoi(exp_env("DBHIP_SORT_ONESWEEP")) == 0;
-  const bool onesweep = !onesweep_off && big_tiles && m >= (1 << 20);
+  // onesweep (above) for sorts of 2^20 rows and more
+  const bool onesweep = m >= (1 << 20);
   unsigned long long* os_ws = nullptr;   // [8][256] digit histograms | [8] x (ticket, stall flag) | [ntiles][256] status words (cleared per pass)
   const size_t os_words = (size_t)8 * 256 + 16 + (size_t)ntiles * 256;
   if (onesweep) {
@@ -1009,16 +1006,16 @@ int32_t dbhip_sort_perm(const dbhip_col* keys, const uint8_t* desc_host, const u
     for (int b = 0; b < nbytes; ++b) {
       if (((vary >> (8 * b)) & 0xFF) == 0) continue;  // every image has the same byte here
       DBHIP_POLL_CANCEL(s, "dbhip_sort_perm");
-#define RS_PASS(K_, NT_, KEYS_, OUT_)                                                                                                     \
+#define RS_PASS(K_)                                                                                                                       \
   do {                                                                                                                                    \
-    hipLaunchKernelGGL((sort_hist_kernel<K_, NT_>), dim3((unsigned)ntiles), dim3(NT_), 0, s, (const K_*)(KEYS_), m, 8 * b, hist, ntiles);  \
+    hipLaunchKernelGGL((sort_hist_kernel<K_, 512>), dim3((unsigned)ntiles), dim3(512), 0, s, (const K_*)kb[cur], m, 8 * b, hist, ntiles);  \
     int32_t rc_ = dbscan::exclusive_scan_u32(hist, nh, blk, offs, s);                                                                     \
     if (rc_) return rc_;                                                                                                                  \
-    hipLaunchKernelGGL((sort_scatter_kernel<K_, NT_>), dim3((unsigned)ntiles), dim3(NT_), 0, s, (const K_*)(KEYS_), pb[cur], m, 8 * b,    \
-                       offs, ntiles, b == last_b ? (K_*)nullptr : (K_*)(OUT_), (b == last_b && final_vals) ? final_vals : pb[cur ^ 1]);   \
+    hipLaunchKernelGGL((sort_scatter_kernel<K_, 512>), dim3((unsigned)ntiles), dim3(512), 0, s, (const K_*)kb[cur], pb[cur], m, 8 * b,    \
+                       offs, ntiles, b == last_b ? (K_*)nullptr : (K_*)kb[cur ^ 1], (b == last_b && final_vals) ? final_vals : pb[cur ^ 1]);  \
   } while (0)
-      if (narrow) { if (big_tiles) RS_PASS(uint32_t, 512, kb[cur], kb[cur ^ 1]); else RS_PASS(uint32_t, 256, kb[cur], kb[cur ^ 1]); }
-      else { if (big_tiles) RS_PASS(uint64_t, 512, kb[cur], kb[cur ^ 1]); else RS_PASS(uint64_t, 256, kb[cur], kb[cur ^ 1]); }
+      if (narrow) RS_PASS(uint32_t);
+      else RS_PASS(uint64_t);
 #undef RS_PASS
       if (b == last_b && final_vals) wrote_final = true;
       cur ^= 1;

@@ -847,12 +847,12 @@ __global__ __launch_bounds__(TQ * 2) __attribute__((amdgpu_waves_per_eu(TQ == 25
 // The epilogue is the bound test of bf16_filter_kernel on the 16 x 16 fragment layout.
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
-// V = 1 (round 6): a phase's fragment reads are split at the k half. The k = 0 half is read before the phase's first barrier as before;
+// Round 6: a phase's fragment reads are split at the k half. The k = 0 half is read before the phase's first barrier as before;
 // the k = 1 half is issued right AFTER the cluster's first MFMA pair and lands behind the k = 0 MFMAs — the matrix pipe starts after 4 (2)
 // ds_read_b128 instead of 8 (4), and half of every phase's LDS latency disappears behind MFMA issue. (The compiler waits lgkmcnt(0)
 // before the first MFMA that uses a pending fragment and does not count: reads issued before that MFMA would be waited for as well,
-// hence the placement behind it, pinned with sched_barrier.) V = 0: rounds 4-5.
-template <int METRIC, int V = 1>
+// hence the placement behind it, pinned with sched_barrier.)
+template <int METRIC>
 __global__ __launch_bounds__(512) void bf16_filter256_kernel(HArgs A) {
   extern __shared__ __attribute__((aligned(1024))) uint8_t fsm[];   // 2 buffers x 4 units x 16 KB
   constexpr int TQ = 256, TI = 256;
@@ -922,19 +922,12 @@ __global__ __launch_bounds__(512) void bf16_filter256_kernel(HArgs A) {
   bf16x8 fa[4][2], fb0[2][2], fb1[2][2];
   auto read_a = [&](int buf, int un, int half = 0) {
     const uint8_t* base = fsm + buf * 65536 + un * 16384;
-    if (V == 1) {
 #pragma unroll
-      for (int m = 0; m < 4; ++m) fa[m][half] = __builtin_bit_cast(bf16x8, *(const u32x4*)(base + aoffs(m, half)));
-      return;
-    }
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) fa[m][kk] = __builtin_bit_cast(bf16x8, *(const u32x4*)(base + aoffs(m, kk)));
+    for (int m = 0; m < 4; ++m) fa[m][half] = __builtin_bit_cast(bf16x8, *(const u32x4*)(base + aoffs(m, half)));
   };
   auto read_b = [&](int buf, int un, bf16x8 (&fb)[2][2], int half = -1) {
     const uint8_t* base = fsm + buf * 65536 + un * 16384;
-    if (V == 1 && half >= 0) {
+    if (half >= 0) {
 #pragma unroll
       for (int nn = 0; nn < 2; ++nn) fb[nn][half] = __builtin_bit_cast(bf16x8, *(const u32x4*)(base + boffs(nn, half)));
       return;
@@ -950,7 +943,7 @@ __global__ __launch_bounds__(512) void bf16_filter256_kernel(HArgs A) {
 #pragma unroll
     for (int nn = 0; nn < 4; ++nn) acc[m][nn] = f32x4v{0.f, 0.f, 0.f, 0.f};
   // 16 MFMAs: quadrant (sa, sb) of the wave's 8 x 4 fragments
-  // `fresh` (V = 1): what this phase's own reads deliver — 1: the A fragments of unit (rbuf, run), 2: the B fragments of unit (rbuf, run)
+  // `fresh`: what this phase's own reads deliver — 1: the A fragments of unit (rbuf, run), 2: the B fragments of unit (rbuf, run)
   // into `fb`, 0: nothing the cluster uses (the phase that reads B0 of the NEXT k-tile works from registers and reads both halves up front)
   auto mfma_quadrant = [&](int sa, int sb, bf16x8 (&fb)[2][2], int fresh = 0, int rbuf = 0, int run = 0) {
     __builtin_amdgcn_s_setprio(1);
@@ -961,7 +954,7 @@ __global__ __launch_bounds__(512) void bf16_filter256_kernel(HArgs A) {
 #pragma unroll
         for (int nn = 0; nn < 2; ++nn)
           acc[sa * 4 + m][sb * 2 + nn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[m][kk], fb[nn][kk], acc[sa * 4 + m][sb * 2 + nn], 0, 0, 0);
-        if (V == 1 && fresh != 0 && kk == 0 && m == 0) {   // the k = 1 half, behind the first MFMA pair
+        if (fresh != 0 && kk == 0 && m == 0) {   // the k = 1 half, behind the first MFMA pair
           __builtin_amdgcn_sched_barrier(0);
           if (fresh == 1) read_a(rbuf, run, 1); else read_b(rbuf, run, fb, 1);
           __builtin_amdgcn_sched_barrier(0);
@@ -978,8 +971,7 @@ __global__ __launch_bounds__(512) void bf16_filter256_kernel(HArgs A) {
   // i.e. at least two barriers later for either half. WAR: a unit is restaged two phases after its last read.
 #define F256_MEM_SYNC()                              \
   asm volatile("s_waitcnt vmcnt(10)" ::: "memory");  \
-  __builtin_amdgcn_s_barrier();                      \
-  if (V == 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
+  __builtin_amdgcn_s_barrier()
 #define F256_END_SYNC() __builtin_amdgcn_s_barrier()
 
   // LDS reads per phase are BALANCED (8 / 4 / 8 / 4 ds_read_b128 per wave): B0 of the NEXT k-tile is read in phase 4, whose own MFMAs
@@ -1008,7 +1000,7 @@ __global__ __launch_bounds__(512) void bf16_filter256_kernel(HArgs A) {
       F256_MEM_SYNC();
       mfma_quadrant(0, 0, bx, 1, 0, 0);
       F256_END_SYNC();
-      read_b(0, 3, by, V == 1 ? 0 : -1);
+      read_b(0, 3, by, 0);
       stage(2, 0, g + 2);
       F256_MEM_SYNC();
       mfma_quadrant(0, 1, by, 2, 0, 3);
@@ -1029,7 +1021,7 @@ __global__ __launch_bounds__(512) void bf16_filter256_kernel(HArgs A) {
       F256_MEM_SYNC();
       mfma_quadrant(0, 0, by, 1, 1, 0);
       F256_END_SYNC();
-      read_b(1, 3, bx, V == 1 ? 0 : -1);
+      read_b(1, 3, bx, 0);
       stage(2, 1, g + 3);
       F256_MEM_SYNC();
       mfma_quadrant(0, 1, bx, 2, 1, 3);
@@ -1214,9 +1206,8 @@ int32_t index_search_batch(dbhip_vec_index* ix, const float* queries, int nq, in
     A.tau = out_dist + (k - 1); A.tau_stride = k;
     A.n = hi - lo; A.dpad = dpad; A.nq = nq;
     const bool tall = nq > 128;  // 256-query tiles once there are enough queries to fill them
-    // the 256 x 256 8-phase kernel (round 4) when the k-tiles pair up and the range fills the chip; DBHIP_BF16_256=0: the r01 kernel
-    static const bool f256_off = exp_env("DBHIP_BF16_256") && atoi(exp_env("DBHIP_BF16_256")) == 0;
-    const bool f256 = tall && !f256_off && (dpad / HBK) % 2 == 0 && dpad >= 128 && A.n >= 256;
+    // the 256 x 256 8-phase kernel (round 4) when the k-tiles pair up and the range fills the chip
+    const bool f256 = tall && (dpad / HBK) % 2 == 0 && dpad >= 128 && A.n >= 256;
     A.n_qtiles = (int)ceil_div(nq, tall ? 256 : 128);
     A.n_itiles = ceil_div(A.n, f256 ? 256 : 128);
     A.c = (float)dim * 1.1920929e-07f + 2e-4f;
@@ -1226,10 +1217,9 @@ int32_t index_search_batch(dbhip_vec_index* ix, const float* queries, int nq, in
       static std::once_flag raised_once;
       static hipError_t raised_err = hipSuccess;
       std::call_once(raised_once, [] {
-        raised_err = hipFuncSetAttribute((const void*)bf16_filter256_kernel<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-        if (raised_err == hipSuccess) raised_err = hipFuncSetAttribute((const void*)bf16_filter256_kernel<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-        if (raised_err == hipSuccess) raised_err = hipFuncSetAttribute((const void*)bf16_filter256_kernel<2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-        if (raised_err == hipSuccess) raised_err = hipFuncSetAttribute((const void*)bf16_filter256_kernel<0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+        raised_err = hipFuncSetAttribute((const void*)bf16_filter256_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+        if (raised_err == hipSuccess) raised_err = hipFuncSetAttribute((const void*)bf16_filter256_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+        if (raised_err == hipSuccess) raised_err = hipFuncSetAttribute((const void*)bf16_filter256_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
       });
       DBHIP_CHECK(raised_err);
       A.qcB = qcB; A.qcG = qcG; A.qcT = qcT;
@@ -1239,10 +1229,7 @@ int32_t index_search_batch(dbhip_vec_index* ix, const float* queries, int nq, in
         hipLaunchKernelGGL((bf16_filter256_kernel<2>), fg, dim3(512), 131072, s, A);
       } else if (cosine) {
         hipLaunchKernelGGL((bf16_qcoef_kernel<0>), cg, dim3(256), 0, s, A, nq_pad, qcB, qcG, qcT);
-        // (experiments build: DBHIP_BF16_V=0 runs the rounds-4-5 schedule of the cosine kernel for a same-process A/B)
-        static const bool v0 = exp_env("DBHIP_BF16_V") && atoi(exp_env("DBHIP_BF16_V")) == 0;
-        if (v0) hipLaunchKernelGGL((bf16_filter256_kernel<0, 0>), fg, dim3(512), 131072, s, A);
-        else hipLaunchKernelGGL((bf16_filter256_kernel<0, 1>), fg, dim3(512), 131072, s, A);
+        hipLaunchKernelGGL((bf16_filter256_kernel<0>), fg, dim3(512), 131072, s, A);
       } else {
         hipLaunchKernelGGL((bf16_qcoef_kernel<1>), cg, dim3(256), 0, s, A, nq_pad, qcB, qcG, qcT);
         hipLaunchKernelGGL((bf16_filter256_kernel<1>), fg, dim3(512), 131072, s, A);

@@ -33,15 +33,12 @@ uint64_t* pinned_words(int slot);
 void kernel_timer_start(hipStream_t s);
 void kernel_timer_stop(hipStream_t s);
 
-// Tuning knobs of the development sweeps (grid sizes, kernel variants, thresholds; DESIGN.md names them where it quotes a sweep): compiled
-// in only with -DDBHIP_EXPERIMENTS (`make EXPERIMENTS=1`). The shipped library does not read them — its behaviour is a function of its
-// arguments and of the documented configuration variables (DBHIP_TRACE, DBHIP_JIT_CACHE_DIR, DBHIP_JIT_ARCH, DBHIP_FAGG_JIT,
-// DBHIP_COMM_TIMEOUT_S, DBHIP_CACHE_BYTES) only, and no variable of either kind skips work (tests/test_abi.py checks the binary).
-#ifdef DBHIP_EXPERIMENTS
-inline const char* exp_env(const char* name) { return getenv(name); }
-#else
-inline const char* exp_env(const char*) { return nullptr; }
-#endif
+// The library's behaviour is a function of its arguments and of the documented configuration variables (DBHIP_TRACE,
+// DBHIP_JIT_CACHE_DIR, DBHIP_JIT_ARCH, DBHIP_FAGG_JIT, DBHIP_COMM_TIMEOUT_S, DBHIP_CACHE_BYTES) only, and none of them skips work
+// (tests/test_abi.py checks the binary).
+
+// DBHIP_TRACE set (read once per process): one line "[dbhip] <fmt>" on stderr per decision of an adaptive path
+void trace(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
@@ -50,13 +47,9 @@ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // `cap`: workgroups of a grid-stride streaming kernel. 2048 (8 per CU) suits kernels with 16 B per lane in flight;
 // kernels that keep 32+ B per operand per lane in flight stream FASTER from fewer workgroups (r01x sweep: `plus`
 // 0.69 -> 0.71 at 1024, fused sum(a+b*c) 0.67 -> 0.79 at 512), always whole multiples of the 256 CUs.
-// env DBHIP_GRID_CAP overrides every kernel (experiments).
-int grid_cap_override();
 inline int grid_for(int64_t n_items_per_thread_units, int block, int cap = 2048) {
   int64_t need = ceil_div(n_items_per_thread_units, block);
   if (need < 1) need = 1;
-  const int o = grid_cap_override();
-  if (o > 0) cap = o;
   if (need > cap) need = cap;
   return (int)need;
 }

@@ -89,9 +89,17 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-int grid_cap_override() {
-  static const int cap = [] { const char* e = exp_env("DBHIP_GRID_CAP"); int v = e ? atoi(e) : 0; return v > 0 ? v : 0; }();
-  return cap;
+void trace(const char* fmt, ...) {
+  static const bool on = getenv("DBHIP_TRACE") != nullptr;
+  if (!on) return;
+  va_list ap;
+  va_start(ap, fmt);
+  flockfile(stderr);   // (one line, whatever other threads write)
+  fputs("[dbhip] ", stderr);
+  vfprintf(stderr, fmt, ap);
+  fputc('\n', stderr);
+  funlockfile(stderr);
+  va_end(ap);
 }
 
 int32_t hip_fail(hipError_t e, const char* what) {

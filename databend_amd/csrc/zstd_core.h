@@ -12,7 +12,7 @@
 //     put_in(pos, len)      a Raw_Block
 //     put_fill(byte, len)   an RLE_Block
 //     put_match(off, len)   a back-reference
-// The file compiles for the device (k_parquet_dev.hip: W = the wave of dv_inflate_zstd_kernel) and for the host
+// The file compiles for the device (k_parquet_dev.hip: W = the producer wave of dv_inflate_zstd2_kernel, dv_wave.h ZProd) and for the host
 // (tests/zstd_host_check.cpp: W = plain memory), so that the parse logic is fuzzed against the system's libzstd on the CPU; the
 // product only ever instantiates it on the device.
 //

@@ -3,10 +3,9 @@
 reports what the hardware will run: registers, scratch, and the instruction mix of its loops (tools/isa_loops.py). This is how
 the specialised kernels are optimised offline; one GPU run then confirms the time.
 
-    python tools/jit_offline.py [q1|plain4] [--slots 4] [--defs "-DFA_JIT_ROWS=4"] [--keep /tmp/out]
+    python tools/jit_offline.py [q1|plain4] [--slots 4] [--keep /tmp/out]
 
-(--defs goes through DBHIP_FAGG_JIT_DEFS, which only an experiments build of the library reads: `make -C databend_amd/csrc clean all EXPERIMENTS=1`;
---slots 260 = 4 slots + 0x100: the FA_MULTI specialisation of a pipelined table's multi-block launches.)
+(--slots 260 = 4 slots + 0x100: the FA_MULTI specialisation of a pipelined table's multi-block launches.)
 """
 import argparse
 import ctypes as C
@@ -78,11 +77,9 @@ def general_shape():
     return [L.T_I64], [0], aggs, [FakeCol(L.T_I64)], p, [("input", 0), None, ("input", 1), ("input", 0)], -1
 
 
-def compile_shape(shape, slots, defs):
+def compile_shape(shape, slots):
     key_types, key_nullable, aggs, keys, p, arg_regs, filter_reg = shape
     lib = L.load_library()
-    if defs:
-        os.environ["DBHIP_FAGG_JIT_DEFS"] = defs
     kt = (C.c_int32 * len(key_types))(*key_types)
     kn = (C.c_uint8 * len(key_types))(*key_nullable)
     ad = (L.AggDesc * len(aggs))()
@@ -112,10 +109,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("shape", nargs="?", default="q1")
     ap.add_argument("--slots", type=int, default=4)
-    ap.add_argument("--defs", default="")
     ap.add_argument("--keep", default="/tmp/jit_offline")
     a = ap.parse_args()
-    code = compile_shape({"q1": q1_shape, "q1rescale": q1_rescale_shape, "plain4": plain4_shape, "general": general_shape}[a.shape](), a.slots, a.defs)
+    code = compile_shape({"q1": q1_shape, "q1rescale": q1_rescale_shape, "plain4": plain4_shape, "general": general_shape}[a.shape](), a.slots)
     open(a.keep + ".co", "wb").write(code)
     llvm = "/opt/rocm/lib/llvm/bin"
     asm = subprocess.run([f"{llvm}/llvm-objdump", "-d", a.keep + ".co"], capture_output=True, text=True, check=True).stdout
