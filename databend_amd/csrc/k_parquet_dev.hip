@@ -19,6 +19,8 @@
 //   dv_values_kernel    one workgroup per data page: PLAIN (fixed width, BOOLEAN bits, BYTE_ARRAY length chain -> 16-byte views
 //                       that point into the image), PLAIN_DICTIONARY / RLE_DICTIONARY (hybrid walk of the indices + gather), RLE
 //                       booleans, DELTA_BINARY_PACKED (INT32 / INT64: block / miniblock walk, workgroup prefix sum of the deltas).
+//   dv_values_ext_kernel BYTE_STREAM_SPLIT, DELTA_LENGTH_BYTE_ARRAY (views into the image), DELTA_BYTE_ARRAY (views into the chunk's
+//                       arena, which dv_dba_size_kernel sizes and dv_dba_replay_kernel fills) — launched only for batches with such pages.
 //   pq_popc / scan / pq_spread (pq_common.h)   nullable columns: dense values -> rows.
 // Nothing is validated on the host beyond the page table, so every device access is checked against the page payload, the
 // dictionary and the output size; the first violation is recorded in a device word and decode returns DBHIP_ERR_INVALID.
@@ -35,7 +37,11 @@
 namespace {
 
 enum { DV_OK = 0, DV_CORRUPT = 1, DV_UNSUPPORTED = 2 };
-enum { ENC_DELTA_BINARY_PACKED = 5 };
+enum { ENC_DELTA_BINARY_PACKED = 5, ENC_DELTA_LENGTH_BYTE_ARRAY = 6, ENC_DELTA_BYTE_ARRAY = 7, ENC_BYTE_STREAM_SPLIT = 9 };
+// the encodings dv_values_ext_kernel decodes (dv_values_kernel never sees their pages)
+__host__ __device__ __forceinline__ bool dv_ext_enc(uint32_t e) {
+  return e == ENC_DELTA_LENGTH_BYTE_ARRAY || e == ENC_DELTA_BYTE_ARRAY || e == ENC_BYTE_STREAM_SPLIT;
+}
 enum { CODEC_NONE = 0, CODEC_SNAPPY = 1, CODEC_ZSTD = 6, CODEC_LZ4_RAW = 7 };
 
 __device__ __forceinline__ void dv_fail(uint32_t* ctl, uint32_t code) { atomicCAS(&ctl[0], 0u, code); }
@@ -605,9 +611,12 @@ struct DvDeltaShared {
 };
 
 // DELTA_BINARY_PACKED (Encodings.md): <block size> <miniblocks per block> <total count> <first value>, then per block
-// <min delta> <bit width per miniblock> <miniblocks>. `count` values -> out[o0 ..).
-__device__ bool dv_delta(const uint8_t* __restrict__ s, uint32_t rlen, uint32_t count, const PqConv& cv, void* __restrict__ out, uint64_t o0,
-                         DvDeltaShared* S) {
+// <min delta> <bit width per miniblock> <miniblocks>. The first `count` values -> put(i, v) (called by the thread that owns value i);
+// exact: the stream holds exactly `count` values (the length streams of DELTA_(LENGTH_)BYTE_ARRAY). *end: where the stream ends (past the
+// last miniblock that holds a value).
+template <class Put>
+__device__ __forceinline__ bool dv_delta_walk(const uint8_t* __restrict__ s, uint32_t rlen, uint32_t count, bool exact, DvDeltaShared* S, Put&& put,
+                                              uint32_t* end) {
   const uint32_t tid = threadIdx.x;
   uint32_t pos = 0;
   uint64_t bs, mb, total, zz;
@@ -616,10 +625,11 @@ __device__ bool dv_delta(const uint8_t* __restrict__ s, uint32_t rlen, uint32_t 
   if (mb == 0 || mb > 4096 || bs == 0 || bs > (1u << 24) || bs % mb != 0) return false;
   const uint32_t vpm = (uint32_t)(bs / mb);
   if (vpm % 8 != 0) return false;
-  if (total < (uint64_t)count) return false;
+  if (total < (uint64_t)count || (exact && total != (uint64_t)count)) return false;
+  *end = pos;
   if (count == 0) return true;
   uint64_t last = (zz >> 1) ^ (0 - (zz & 1));
-  if (tid == 0) dv_store_int(cv, out, o0, last);
+  if (tid == 0) put(0u, last);
   uint32_t produced = 1;
   while (produced < count) {
     uint64_t mz;
@@ -647,7 +657,7 @@ __device__ bool dv_delta(const uint8_t* __restrict__ s, uint32_t rlen, uint32_t 
         __syncthreads();
         uint64_t wb = last;
         for (uint32_t w = 0; w < (tid >> 6); ++w) wb += S->wt[w];
-        if (i < need) dv_store_int(cv, out, o0 + produced + i, wb + incl);
+        if (i < need) put(produced + i, wb + incl);
         last += S->wt[0] + S->wt[1] + S->wt[2] + S->wt[3];
       }
       const uint64_t mbytes = ((uint64_t)vpm * b) >> 3;
@@ -655,7 +665,15 @@ __device__ bool dv_delta(const uint8_t* __restrict__ s, uint32_t rlen, uint32_t 
       produced += need;
     }
   }
+  *end = pos;
   return true;
+}
+
+// DELTA_BINARY_PACKED values (INT32 / INT64) -> out[o0 ..)
+__device__ bool dv_delta(const uint8_t* __restrict__ s, uint32_t rlen, uint32_t count, const PqConv& cv, void* __restrict__ out, uint64_t o0,
+                         DvDeltaShared* S) {
+  uint32_t end;
+  return dv_delta_walk(s, rlen, count, false, S, [&](uint32_t i, uint64_t v) { dv_store_int(cv, out, o0 + i, v); }, &end);
 }
 
 __device__ __forceinline__ void dv_put_dict(const PqConv& cv, const void* __restrict__ dict, uint32_t idx, void* __restrict__ out, uint64_t o) {
@@ -763,6 +781,249 @@ __global__ __launch_bounds__(256) void dv_values_kernel(const DvChunkD* __restri
   if (!ok) dv_fail(ctl, DV_CORRUPT);
 }
 
+// ---------------------------------------------------------------------------------------------
+// DELTA_LENGTH_BYTE_ARRAY, DELTA_BYTE_ARRAY, BYTE_STREAM_SPLIT (Encodings.md): kernels of their own, launched only for batches that
+// hold such pages, so that dv_values_kernel (the scan's hot path) keeps its registers and LDS
+// ---------------------------------------------------------------------------------------------
+// one data page in one of those encodings
+struct DvXJob {
+  uint32_t k, d;        // chunk of the batch, data page of the chunk
+  uint32_t enc, sec;    // encoding; DELTA_BYTE_ARRAY: where the suffix bytes start, from the page's values (dv_dba_size_kernel)
+  uint32_t* lens;       // DELTA_(LENGTH_)BYTE_ARRAY: scratch for the lengths (DELTA_BYTE_ARRAY: the prefix lengths, then the suffix lengths)
+  uint8_t* dst;         // DELTA_BYTE_ARRAY: the page's values in the chunk's arena
+  uint64_t aoff;        // DELTA_BYTE_ARRAY: offset of dst in the arena
+  uint64_t bytes;       // DELTA_BYTE_ARRAY: bytes of the page's values (dv_dba_size_kernel)
+  uint32_t live, pad;   // DELTA_BYTE_ARRAY: 1 = the chunk passed its sizing checks and has its arena (set by the host)
+};
+
+// 16-byte view of the `len` bytes at p, which lie at offset `off` of buffer `buf` of the column (store_view for a length known apart)
+__device__ __forceinline__ void dv_view(const uint8_t* __restrict__ p, uint32_t len, uint32_t buf, uint32_t off, void* __restrict__ out, uint64_t o) {
+  uint32_t w1 = 0, w2 = 0, w3 = 0;
+  if (len <= 12) {
+#pragma unroll
+    for (uint32_t b = 0; b < 12; ++b) {
+      const uint32_t x = b < len ? (uint32_t)p[b] << (8 * (b & 3)) : 0u;
+      if (b < 4) w1 |= x; else if (b < 8) w2 |= x; else w3 |= x;
+    }
+  } else {
+    w1 = (uint32_t)load_le(p, 4);
+    w2 = buf;
+    w3 = off;
+  }
+  ((uint4*)out)[o] = make_uint4(len, w1, w2, w3);
+}
+
+// exclusive prefix sum of v over the workgroup (256 threads); *tot: the workgroup's sum. Called by all threads.
+__device__ __forceinline__ uint64_t dv_block_xscan(uint64_t v, uint64_t* wt, uint64_t* tot) {
+  const uint32_t tid = threadIdx.x;
+  uint64_t incl = v;
+  for (int dd = 1; dd < 64; dd <<= 1) {
+    const uint64_t t = __shfl_up(incl, dd, 64);
+    if ((int)(tid & 63) >= dd) incl += t;
+  }
+  __syncthreads();
+  if ((tid & 63) == 63) wt[tid >> 6] = incl;
+  __syncthreads();
+  uint64_t wb = 0;
+  for (uint32_t w = 0; w < (tid >> 6); ++w) wb += wt[w];
+  *tot = wt[0] + wt[1] + wt[2] + wt[3];
+  return wb + incl - v;
+}
+
+// value i of a BYTE_STREAM_SPLIT page of n values (byte k of value i at s[k n + i]) -> element o of out, converted as store_plain converts
+// the same bytes in PLAIN order (the bytes are gathered into registers, not into a private array)
+__device__ __forceinline__ void dv_store_bss(const PqConv& cv, const uint8_t* __restrict__ s, uint32_t n, uint32_t i, void* __restrict__ out, uint64_t o) {
+  if (cv.physical == PT_FLBA) {
+    // big-endian two's complement of type_length (1..16) bytes
+    const int L = cv.type_length;
+    u128 v = (s[i] & 0x80) ? ~(u128)0 : (u128)0;
+#pragma unroll
+    for (int b = 0; b < 16; ++b)
+      if (b < L) v = (v << 8) | s[(uint64_t)b * n + i];
+    if (cv.esize == 16) ((u128*)out)[o] = v; else ((uint64_t*)out)[o] = (uint64_t)v;
+    return;
+  }
+  const int w = (cv.physical == PT_INT32 || cv.physical == PT_FLOAT) ? 4 : 8;
+  uint64_t v = 0;
+#pragma unroll
+  for (int b = 0; b < 8; ++b)
+    if (b < w) v |= (uint64_t)s[(uint64_t)b * n + i] << (8 * b);
+  if (w == 4) {
+    const uint32_t x = (uint32_t)v;
+    switch (cv.esize) {
+      case 1: ((uint8_t*)out)[o] = (uint8_t)x; break;
+      case 2: ((uint16_t*)out)[o] = (uint16_t)x; break;
+      case 4: ((uint32_t*)out)[o] = x; break;
+      default: ((int64_t*)out)[o] = (int64_t)(int32_t)x; break;
+    }
+    return;
+  }
+  if (cv.esize == 16) ((i128*)out)[o] = (i128)(int64_t)v; else ((uint64_t*)out)[o] = v;
+}
+
+// DELTA_BYTE_ARRAY, step 1 (after dv_scan_kernel: the page's non-null count is known). One workgroup per page: both length streams
+// -> scratch, checked (prefix[0] = 0, prefix[i] <= length of value i - 1, no negative length, each stream holds exactly the page's
+// count, the suffixes fit the bytes after the streams, FIXED_LEN_BYTE_ARRAY: every value is type_length long) -> the page's bytes of
+// values and where its suffix bytes start. The host reads the byte counts back and allocates the arena the values are replayed into.
+__global__ __launch_bounds__(256) void dv_dba_size_kernel(const DvChunkD* __restrict__ cds, DvXJob* __restrict__ jobs) {
+  __shared__ DvDeltaShared S;
+  __shared__ uint64_t wt[4];
+  DvXJob* J = jobs + blockIdx.x;
+  const DvChunkD& C = cds[J->k];
+  const uint32_t d = J->d, tid = threadIdx.x;
+  uint32_t* __restrict__ ctl = C.hdr;
+  const DvPage P = C.pages[C.dp[d]];
+  const uint32_t n = C.nn[d], vo = C.voff[d];
+  const uint64_t o0 = C.vbase[d];
+  if (n == 0) return;
+  if (vo > P.uncomp_len || n > P.num_values || o0 + n > C.rows) { dv_fail(ctl, DV_CORRUPT); return; }
+  const uint8_t* s = C.img + P.img_off + vo;
+  const uint32_t rlen = P.uncomp_len - vo;
+  uint32_t* __restrict__ pre = J->lens;
+  uint32_t* __restrict__ suf = J->lens + n;
+  bool bad = false;
+  uint32_t e1 = 0, e2 = 0;
+  bool ok = dv_delta_walk(s, rlen, n, true, &S, [&](uint32_t i, uint64_t v) { bad |= (int32_t)v < 0; pre[i] = (uint32_t)v; }, &e1);
+  ok = ok && dv_delta_walk(s + e1, rlen - e1, n, true, &S, [&](uint32_t i, uint64_t v) { bad |= (int32_t)v < 0; suf[i] = (uint32_t)v; }, &e2);
+  if (__syncthreads_or(!ok || bad)) { dv_fail(ctl, DV_CORRUPT); return; }   // (also: the lengths are visible to the workgroup)
+  const uint32_t sec = e1 + e2;
+  const bool fixed = C.cv.physical == PT_FLBA;
+  const uint64_t tl = (uint64_t)C.cv.type_length;
+  uint64_t sufsum = 0, lensum = 0;
+  for (uint32_t i = tid; i < n; i += 256) {
+    const uint32_t p = pre[i], q = suf[i];
+    if (i == 0 ? p != 0 : (uint64_t)p > (uint64_t)pre[i - 1] + suf[i - 1]) bad = true;
+    if (fixed && (uint64_t)p + q != tl) bad = true;
+    sufsum += q;
+    lensum += (uint64_t)p + q;
+  }
+  uint64_t st, lt;
+  (void)dv_block_xscan(sufsum, wt, &st);
+  (void)dv_block_xscan(lensum, wt, &lt);
+  if (__syncthreads_or(bad) || st > (uint64_t)(rlen - sec)) { dv_fail(ctl, DV_CORRUPT); return; }
+  if (tid == 0) { J->sec = sec; J->bytes = lt; }
+}
+
+// DELTA_BYTE_ARRAY, step 2: the values into the arena. Value i is the first prefix[i] bytes of value i - 1, then suffix i — an LZ77
+// sequence stream: sequence i is the literal suffix i, then a match of prefix[i + 1] bytes at distance len(value i). One wave per page
+// replays it with ZWave (dv_wave.h: 64 sequences per step, one lane per output byte, an LDS ring, references beyond it read from the
+// arena), the suffixes read from the page as one forward stream. The sizing kernel has checked every sequence.
+__global__ __launch_bounds__(64) void dv_dba_replay_kernel(const DvChunkD* __restrict__ cds, const DvXJob* __restrict__ jobs, uint32_t ring) {
+  extern __shared__ __align__(16) uint8_t dv_lds[];
+  const DvXJob J = jobs[blockIdx.x];
+  if (!J.live || J.bytes == 0) return;
+  const DvChunkD& C = cds[J.k];
+  const DvPage P = C.pages[C.dp[J.d]];
+  const uint32_t n = C.nn[J.d], vo = C.voff[J.d];
+  const uint32_t lane = threadIdx.x;
+  const uint8_t* s = C.img + P.img_off + vo;
+  const uint32_t rlen = P.uncomp_len - vo;
+  DvJob Q;
+  Q.src = s; Q.dst = J.dst;
+  Q.comp_len = rlen; Q.uncomp_len = (uint32_t)J.bytes; Q.lev_len = 0; Q.compressed = 1;
+  // readable: the page's bytes up to the next 4-byte boundary (image pages start 16-byte aligned and the image has 16 bytes of slack;
+  // an UNCOMPRESSED chunk is readable up to the 16-byte boundary past its end)
+  const uint32_t a = (uint32_t)((uintptr_t)s & 3u);
+  Q.src_safe = ((a + rlen + 3u) & ~3u) - a;
+  Q.codec = 0; Q.ctl = C.hdr;
+  ZWave w;
+  w.begin(Q, dv_lds, ring, lane);
+  // replay() rejects a batch whose matches reach before the frame; every match here is checked, and a lane without a match (ml = 0)
+  // carries off = 1, which must pass even before the first byte (a page that starts with empty strings): the frame starts one byte early
+  w.frame0 = ~0u;
+  FwdStream ls;
+  uint32_t lp = w.a0 + J.sec;
+  ls.open(w.srcA, w.safeA, lp, lane);
+  const uint32_t* __restrict__ pre = J.lens;
+  const uint32_t* __restrict__ suf = J.lens + n;
+  for (uint32_t b0 = 0; b0 < n; b0 += 64) {
+    const uint32_t m = n - b0 < 64 ? n - b0 : 64;
+    const uint32_t i = b0 + lane;
+    uint32_t ll = 0, ml = 0, off = 1;
+    if (lane < m) {
+      ll = suf[i];
+      ml = i + 1 < n ? pre[i + 1] : 0u;
+      off = ml ? pre[i] + ll : 1u;
+    }
+    uint32_t lits = 0;
+    (void)w.replay<true>(ls, m, ll, ml, off, lp, false, lits);
+    lp = rfl(lp + lits);
+  }
+  w.flush(true);
+}
+
+// the values of the pages in those encodings; one workgroup per (page, slice) — BYTE_STREAM_SPLIT and FIXED_LEN_BYTE_ARRAY from the arena
+// are split like PLAIN fixed-width pages, the others run in slice 0
+__global__ __launch_bounds__(256) void dv_values_ext_kernel(const DvChunkD* __restrict__ cds, const DvXJob* __restrict__ jobs) {
+  __shared__ DvDeltaShared S;
+  __shared__ uint64_t wt[4];
+  const DvXJob J = jobs[blockIdx.x];
+  const DvChunkD& C = cds[J.k];
+  if (blockIdx.y >= C.slices) return;
+  const uint32_t d = J.d, tid = threadIdx.x;
+  const PqConv cv = C.cv;
+  void* __restrict__ out = C.target;
+  uint32_t* __restrict__ ctl = C.hdr;
+  const DvPage P = C.pages[C.dp[d]];
+  const uint32_t n = C.nn[d], vo = C.voff[d];
+  const uint64_t o0 = C.vbase[d];
+  if (n == 0) return;
+  if (vo > P.uncomp_len || n > P.num_values || o0 + n > C.rows) { dv_fail(ctl, DV_CORRUPT); return; }
+  const uint8_t* s = C.img + P.img_off + vo;
+  const uint32_t rlen = P.uncomp_len - vo;
+  const uint32_t lo = (uint32_t)((uint64_t)n * blockIdx.y / C.slices), hi = (uint32_t)((uint64_t)n * (blockIdx.y + 1) / C.slices);
+  if (P.enc == ENC_BYTE_STREAM_SPLIT) {
+    // a streaming transpose: lane-consecutive values read consecutive bytes of each of the w streams
+    const uint32_t w = (uint32_t)plain_width(cv.physical, cv.type_length);
+    if (w == 0 || rlen / w < n) { dv_fail(ctl, DV_CORRUPT); return; }
+    for (uint32_t i = lo + tid; i < hi; i += 256) dv_store_bss(cv, s, n, i, out, o0 + i);
+    return;
+  }
+  if (P.enc == ENC_DELTA_BYTE_ARRAY) {
+    if (!J.live) return;   // not materialised: the chunk failed its checks (or its arena would be too large), decode reports it
+    if (cv.physical == PT_FLBA) {
+      const uint32_t w = (uint32_t)cv.type_length;
+      for (uint32_t i = lo + tid; i < hi; i += 256) store_plain(cv, J.dst + (uint64_t)i * w, out, o0 + i);
+      return;
+    }
+    if (blockIdx.y != 0) return;
+    const uint32_t* __restrict__ pre = J.lens;
+    const uint32_t* __restrict__ suf = J.lens + n;
+    uint64_t carry = 0;
+    for (uint32_t c0 = 0; c0 < n; c0 += 256) {
+      const uint32_t i = c0 + tid;
+      const uint32_t len = i < n ? pre[i] + suf[i] : 0u;
+      uint64_t tot;
+      const uint64_t x = carry + dv_block_xscan(len, wt, &tot);
+      if (i < n) dv_view(J.dst + x, len, 1u, (uint32_t)(J.aoff + x), out, o0 + i);   // (the host keeps the arena below 4 GiB)
+      carry += tot;
+    }
+    return;
+  }
+  // DELTA_LENGTH_BYTE_ARRAY: the lengths (DELTA_BINARY_PACKED) -> scratch, then the bytes of all values back to back: views into the page
+  if (blockIdx.y != 0) return;
+  uint32_t* __restrict__ lens = J.lens;
+  bool bad = false;
+  uint32_t e = 0;
+  const bool ok = dv_delta_walk(s, rlen, n, true, &S, [&](uint32_t i, uint64_t v) { bad |= (int32_t)v < 0; lens[i] = (uint32_t)v; }, &e);
+  if (__syncthreads_or(!ok || bad)) { dv_fail(ctl, DV_CORRUPT); return; }
+  uint64_t sum = 0;
+  for (uint32_t i = tid; i < n; i += 256) sum += lens[i];
+  uint64_t total;
+  (void)dv_block_xscan(sum, wt, &total);
+  if (total > (uint64_t)(rlen - e)) { dv_fail(ctl, DV_CORRUPT); return; }
+  const uint64_t base = P.img_off + vo + e;   // offset of the first value's bytes in the image (< 4 GiB: open checked)
+  uint64_t carry = 0;
+  for (uint32_t c0 = 0; c0 < n; c0 += 256) {
+    const uint32_t i = c0 + tid;
+    const uint32_t len = i < n ? lens[i] : 0u;
+    uint64_t tot;
+    const uint64_t x = carry + dv_block_xscan(len, wt, &tot);
+    if (i < n) dv_view(s + e + x, len, 0u, (uint32_t)(base + x), out, o0 + i);
+    carry += tot;
+  }
+}
+
 int32_t dv_unsupported(const char* what) {
   set_error("dbhip_pq_chunk_open_device: %s (use dbhip_pq_chunk_open, or keep the CPU reader for this chunk)", what);
   return DBHIP_ERR_UNSUPPORTED;
@@ -853,9 +1114,18 @@ int32_t open_device_impl(const uint8_t* chunk_host, int64_t chunk_len, int32_t c
         c->dict_n = h.num_values;
       } else {
         const int e = h.encoding;
-        const bool enc_ok = e == ENC_PLAIN || e == ENC_PLAIN_DICT || e == ENC_RLE_DICT || (e == ENC_RLE && c->physical == PT_BOOLEAN) ||
-                            (e == ENC_DELTA_BINARY_PACKED && (c->physical == PT_INT32 || c->physical == PT_INT64));
-        if (!enc_ok) { rc = dv_unsupported("value encoding other than PLAIN / RLE_DICTIONARY / RLE (BOOLEAN) / DELTA_BINARY_PACKED (INT32, INT64)"); break; }
+        const int pt = c->physical;
+        const bool enc_ok = e == ENC_PLAIN || e == ENC_PLAIN_DICT || e == ENC_RLE_DICT || (e == ENC_RLE && pt == PT_BOOLEAN) ||
+                            (e == ENC_DELTA_BINARY_PACKED && (pt == PT_INT32 || pt == PT_INT64)) ||
+                            (e == ENC_DELTA_LENGTH_BYTE_ARRAY && pt == PT_BYTE_ARRAY) ||
+                            (e == ENC_DELTA_BYTE_ARRAY && (pt == PT_BYTE_ARRAY || pt == PT_FLBA)) ||
+                            (e == ENC_BYTE_STREAM_SPLIT && (pt == PT_FLOAT || pt == PT_DOUBLE || pt == PT_INT32 || pt == PT_INT64 || pt == PT_FLBA));
+        if (!enc_ok) {
+          rc = dv_unsupported("value encoding other than PLAIN / RLE_DICTIONARY / RLE (BOOLEAN) / DELTA_BINARY_PACKED (INT32, INT64) / "
+                              "DELTA_LENGTH_BYTE_ARRAY (BYTE_ARRAY) / DELTA_BYTE_ARRAY (BYTE_ARRAY, FIXED_LEN_BYTE_ARRAY) / "
+                              "BYTE_STREAM_SPLIT (FLOAT, DOUBLE, INT32, INT64, FIXED_LEN_BYTE_ARRAY)");
+          break;
+        }
         if ((e == ENC_PLAIN_DICT || e == ENC_RLE_DICT) && c->dict_page < 0) { rc = dv_malformed("dictionary-encoded page without a dictionary page"); break; }
         if (h.type == PG_DATA && c->max_def == 1 && h.def_enc != ENC_RLE) { rc = dv_unsupported("definition levels not RLE encoded"); break; }
         // List mode, v1 pages: dv_levels_kernel reads BOTH level streams as <4-byte length><RLE / bit-packed hybrid runs>; a legacy
@@ -864,6 +1134,11 @@ int32_t open_device_impl(const uint8_t* chunk_host, int64_t chunk_len, int32_t c
         if ((uint64_t)c->rows + (uint64_t)P.num_values >= 0xFFFFFFF0ULL) { rc = dv_unsupported("more than 2^32 rows in one chunk"); break; }
         P.row_start = (uint64_t)c->rows;
         if (!(h.type == PG_DATA_V2 && h.num_nulls == 0) || list_mode) all_v2_no_nulls = false;
+        if (dv_ext_enc((uint32_t)e)) {
+          c->n_ext += 1;
+          if (e == ENC_DELTA_BYTE_ARRAY) { c->n_dba += 1; c->ext_lens += 2 * (int64_t)P.num_values; }
+          else if (e == ENC_DELTA_LENGTH_BYTE_ARRAY) c->ext_lens += (int64_t)P.num_values;
+        }
         c->data_pages.push_back((uint32_t)c->pages.size());
         c->nn_init.push_back(P.num_values);
         c->voff_init.push_back(h.type == PG_DATA_V2 ? P.lev_len : 0u);
@@ -923,7 +1198,7 @@ int32_t dbhip_pq_chunk_open_device_list(const uint8_t* chunk_host, int64_t chunk
 namespace {
 
 struct BlobLayout {
-  size_t hdr, cds, dict_list, lv_map, val_map, jobs, per_chunk, total;
+  size_t hdr, cds, dict_list, lv_map, val_map, jobs, xjobs, per_chunk, total;
 };
 inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 
@@ -934,6 +1209,7 @@ int32_t decode_many(dbhip_pq_chunk* const* cs, int32_t n, const uint8_t* const* 
   hipStream_t s = resolve_stream(stream);
   // ---- checks + what has to be allocated once per chunk
   size_t n_jobs = 0, n_lv = 0, n_dp = 0, per_chunk = 0;
+  size_t n_ext = 0, n_dba = 0, lens_words = 0;   // pages in DELTA_(LENGTH_)BYTE_ARRAY / BYTE_STREAM_SPLIT, of them DELTA_BYTE_ARRAY, scratch for lengths
   std::vector<int> live;      // chunks with rows
   for (int i = 0; i < n; ++i) {
     dbhip_pq_chunk* c = cs[i];
@@ -941,7 +1217,10 @@ int32_t decode_many(dbhip_pq_chunk* const* cs, int32_t n, const uint8_t* const* 
     if (out_status_host) out_status_host[i] = DBHIP_OK;
     DBHIP_REQUIRE(c && c->device_mode, "dbhip_pq_chunk_decode_device: the handle was not opened by dbhip_pq_chunk_open_device");
     DBHIP_REQUIRE(!c->list || list_pass, "dbhip_pq_chunk_decode_device: a List chunk is decoded by dbhip_pq_chunk_decode_device_list");
+    // the arena of the previous decode, if the caller did not take it (dbhip_pq_chunk_take_arena)
+    if (c->d_arena) { (void)dbhip_free(c->d_arena); c->d_arena = nullptr; c->arena_bytes = 0; }
     if (c->rows == 0) continue;
+    n_ext += (size_t)c->n_ext; n_dba += (size_t)c->n_dba; lens_words += (size_t)c->ext_lens;
     DBHIP_REQUIRE(chunk_dev[i] && out_values_dev[i], "dbhip_pq_chunk_decode_device: NULL buffer");
     DBHIP_REQUIRE(((uintptr_t)chunk_dev[i] & 15) == 0, "dbhip_pq_chunk_decode_device: chunk_dev must be 16-byte aligned");
     DBHIP_REQUIRE(c->codec == CODEC_NONE || image_dev[i], "dbhip_pq_chunk_decode_device: a compressed chunk needs an image buffer (info.image_bytes)");
@@ -968,7 +1247,8 @@ int32_t decode_many(dbhip_pq_chunk* const* cs, int32_t n, const uint8_t* const* 
   if (live.empty()) return DBHIP_OK;
   static const bool lds_ok = [] {
     return hipFuncSetAttribute((const void*)dv_inflate_lz_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LZ_RING) == hipSuccess &&
-           hipFuncSetAttribute((const void*)dv_inflate_zstd2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ZW2_LDS) == hipSuccess;
+           hipFuncSetAttribute((const void*)dv_inflate_zstd2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ZW2_LDS) == hipSuccess &&
+           hipFuncSetAttribute((const void*)dv_dba_replay_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LZ_RING) == hipSuccess;
   }();
   if (!lds_ok) { set_error("%s: cannot reserve LDS for the decompression kernels", who); return DBHIP_ERR_HIP; }
   // ---- the blob: everything the kernels read about the batch, one upload
@@ -980,17 +1260,25 @@ int32_t decode_many(dbhip_pq_chunk* const* cs, int32_t n, const uint8_t* const* 
   L.lv_map = L.dict_list + up16(nl * 4);
   L.val_map = L.lv_map + up16(n_lv * 8);
   L.jobs = L.val_map + up16(n_dp * 8);
-  L.per_chunk = L.jobs + up16(n_jobs * sizeof(DvJob));
+  L.xjobs = L.jobs + up16(n_jobs * sizeof(DvJob));
+  L.per_chunk = L.xjobs + up16(n_ext * sizeof(DvXJob));
   L.total = L.per_chunk + per_chunk;
   uint8_t* blob = (uint8_t*)scratch(L.total, 20, s);
   if (!blob) { set_error("%s: out of device memory (%zu bytes of page tables)", who, L.total); return DBHIP_ERR_HIP; }
+  uint32_t* lens = nullptr;
+  if (lens_words) {
+    lens = (uint32_t*)scratch(lens_words * 4 + 64, 21, s);
+    if (!lens) { set_error("%s: out of device memory (%zu bytes of string lengths)", who, lens_words * 4); return DBHIP_ERR_HIP; }
+  }
   std::vector<uint8_t> H(L.total, 0);
   DvChunkD* cds = (DvChunkD*)(H.data() + L.cds);
   uint32_t* dict_list = (uint32_t*)(H.data() + L.dict_list);
   uint2* lv_map = (uint2*)(H.data() + L.lv_map);
   uint2* val_map = (uint2*)(H.data() + L.val_map);
   DvJob* jobs = (DvJob*)(H.data() + L.jobs);
-  size_t at = L.per_chunk, n_dict = 0, k_lv = 0, k_dp = 0;
+  DvXJob* xjobs = (DvXJob*)(H.data() + L.xjobs);   // DELTA_BYTE_ARRAY pages first
+  size_t at = L.per_chunk, n_dict = 0, k_lv = 0, k_dp = 0, k_dba = 0, k_x = n_dba, lens_at = 0;
+  unsigned max_slices_x = 1;
   // jobs: ZSTD pages first (their own kernel), then Snappy / LZ4
   size_t n_z = 0;
   for (int i : live)
@@ -1043,7 +1331,15 @@ int32_t decode_many(dbhip_pq_chunk* const* cs, int32_t n, const uint8_t* const* 
     if (c->dict_n > 0) dict_list[n_dict++] = (uint32_t)k;
     for (uint32_t d = 0; d < nd; ++d) {
       if (c->max_def == 1) lv_map[k_lv++] = make_uint2((unsigned)k, d);
-      val_map[k_dp++] = make_uint2((unsigned)k, d);
+      if (c->n_ext == 0 || !dv_ext_enc(c->pages[c->data_pages[d]].enc)) { val_map[k_dp++] = make_uint2((unsigned)k, d); continue; }
+      const DvPage& P = c->pages[c->data_pages[d]];
+      DvXJob& X = P.enc == ENC_DELTA_BYTE_ARRAY ? xjobs[k_dba++] : xjobs[k_x++];
+      X.k = (uint32_t)k; X.d = d; X.enc = P.enc;
+      if (P.enc != ENC_BYTE_STREAM_SPLIT) {
+        X.lens = lens + lens_at;
+        lens_at += (P.enc == ENC_DELTA_BYTE_ARRAY ? 2 : 1) * (size_t)P.num_values;
+      }
+      if (slices > max_slices_x) max_slices_x = slices;
     }
     if (c->codec != CODEC_NONE) {
       const uint64_t safe_end = ((uint64_t)c->chunk_len + 15) & ~15ull;   // chunk_dev is readable up to here
@@ -1083,7 +1379,42 @@ int32_t decode_many(dbhip_pq_chunk* const* cs, int32_t n, const uint8_t* const* 
   if (n_dict) hipLaunchKernelGGL(dv_dict_kernel, dim3((unsigned)n_dict), dim3(256), 0, s, d_cds, (const uint32_t*)(blob + L.dict_list));
   if (n_lv) hipLaunchKernelGGL(dv_levels_kernel, dim3((unsigned)n_lv), dim3(256), any_list ? LV_LDS : 0u, s, d_cds, (const uint2*)(blob + L.lv_map), any_list ? LV_LDS : 0u);
   hipLaunchKernelGGL(dv_scan_kernel, dim3((unsigned)nl), dim3(256), 0, s, d_cds);
-  if (n_dp) hipLaunchKernelGGL(dv_values_kernel, dim3((unsigned)n_dp, max_slices), dim3(256), 0, s, d_cds, (const uint2*)(blob + L.val_map));
+  if (k_dp) hipLaunchKernelGGL(dv_values_kernel, dim3((unsigned)k_dp, max_slices), dim3(256), 0, s, d_cds, (const uint2*)(blob + L.val_map));
+  // DELTA_BYTE_ARRAY: size every page, read the sizes back (the one extra read-back, only for batches that hold such pages), give each chunk
+  // one arena, replay the values into it
+  DvXJob* d_xjobs = (DvXJob*)(blob + L.xjobs);
+  std::vector<uint8_t> arena_unsupported(nl, 0);
+  if (n_dba) {
+    hipLaunchKernelGGL(dv_dba_size_kernel, dim3((unsigned)n_dba), dim3(256), 0, s, d_cds, d_xjobs);
+    DBHIP_LAUNCH_CHECK();
+    std::vector<uint32_t> hdr0(nl * 8, 0);
+    DBHIP_CHECK(hipMemcpyAsync(hdr0.data(), blob + L.hdr, nl * 32, hipMemcpyDeviceToHost, s));
+    DBHIP_CHECK(hipMemcpyAsync(xjobs, d_xjobs, n_dba * sizeof(DvXJob), hipMemcpyDeviceToHost, s));
+    DBHIP_CHECK(hipStreamSynchronize(s));
+    std::vector<uint64_t> total(nl, 0);
+    for (size_t j = 0; j < n_dba; ++j) {
+      const uint32_t k = xjobs[j].k;
+      if (xjobs[j].bytes >= (1ull << 31)) arena_unsupported[k] = 1;   // (ZWave's replay keeps a page's output below 2^31 bytes)
+      xjobs[j].aoff = total[k];
+      total[k] += xjobs[j].bytes;
+    }
+    for (size_t k = 0; k < nl; ++k) {
+      if (total[k] >= (1ull << 32)) arena_unsupported[k] = 1;         // views carry 32-bit offsets
+      if (total[k] == 0 || hdr0[k * 8] != DV_OK || arena_unsupported[k]) continue;
+      dbhip_pq_chunk* c = cs[live[k]];
+      DBHIP_TRY(dbhip_alloc((size_t)total[k] + 16, &c->d_arena));
+      c->arena_bytes = (int64_t)total[k];
+    }
+    for (size_t j = 0; j < n_dba; ++j) {
+      const uint32_t k = xjobs[j].k;
+      dbhip_pq_chunk* c = cs[live[k]];
+      xjobs[j].live = hdr0[k * 8] == DV_OK && !arena_unsupported[k];
+      xjobs[j].dst = c->d_arena ? (uint8_t*)c->d_arena + xjobs[j].aoff : nullptr;   // (no arena: every value of the chunk is empty)
+    }
+    DBHIP_CHECK(hipMemcpyAsync(d_xjobs, xjobs, n_dba * sizeof(DvXJob), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(dv_dba_replay_kernel, dim3((unsigned)n_dba), dim3(64), LZ_RING, s, d_cds, (const DvXJob*)d_xjobs, LZ_RING);
+  }
+  if (n_ext) hipLaunchKernelGGL(dv_values_ext_kernel, dim3((unsigned)n_ext, max_slices_x), dim3(256), 0, s, d_cds, (const DvXJob*)d_xjobs);
   for (int i : live) {
     dbhip_pq_chunk* c = cs[i];
     if (!(c->max_def == 1 && !c->known_no_nulls)) continue;
@@ -1123,7 +1454,11 @@ int32_t decode_many(dbhip_pq_chunk* const* cs, int32_t n, const uint8_t* const* 
     uint64_t nonnull;
     memcpy(&nonnull, &hdr[k * 8 + 2], 8);
     int32_t rc = DBHIP_OK;
-    if (verdict == DV_UNSUPPORTED) {
+    if (verdict == DV_OK && arena_unsupported[k]) {
+      set_error("dbhip_pq_chunk_decode_device: chunk %d: its DELTA_BYTE_ARRAY values take 4 GiB or more (or 2 GiB or more in one page); "
+                "use the CPU reader for this chunk", i);
+      rc = DBHIP_ERR_UNSUPPORTED;
+    } else if (verdict == DV_UNSUPPORTED) {
       set_error("dbhip_pq_chunk_decode_device: chunk %d uses a form the device path does not decode (a Snappy back-reference beyond 64 KiB, a ZSTD "
                 "dictionary, or an encoding that changes between pages); use dbhip_pq_chunk_open", i);
       rc = DBHIP_ERR_UNSUPPORTED;
@@ -1139,6 +1474,7 @@ int32_t decode_many(dbhip_pq_chunk* const* cs, int32_t n, const uint8_t* const* 
       c->nulls = c->rows - c->nonnull;
       if (out_nulls_host) out_nulls_host[i] = c->nulls;
     }
+    if (rc && c->d_arena) { (void)dbhip_free(c->d_arena); c->d_arena = nullptr; c->arena_bytes = 0; }
     if (out_status_host) out_status_host[i] = rc;
     if (rc && !first_rc) first_rc = rc;
   }
@@ -1327,6 +1663,15 @@ int32_t dbhip_pq_chunk_decode_device_list(dbhip_pq_chunk* c, const uint8_t* chun
                                           int64_t* out_rows_host, int64_t* out_elems_host, int64_t* out_null_lists_host, void* stream) {
   return decode_list(c, chunk_dev, image_dev, out_offsets_dev, out_list_validity_dev, out_values_dev, out_elem_validity_dev, out_rows_host, out_elems_host,
                      out_null_lists_host, stream);
+}
+
+int32_t dbhip_pq_chunk_take_arena(dbhip_pq_chunk* c, void** out_dev_ptr_host, int64_t* out_bytes_host) {
+  DBHIP_REQUIRE(c && out_dev_ptr_host && out_bytes_host, "dbhip_pq_chunk_take_arena: NULL argument");
+  *out_dev_ptr_host = c->d_arena;
+  *out_bytes_host = c->d_arena ? c->arena_bytes : 0;
+  c->d_arena = nullptr;
+  c->arena_bytes = 0;
+  return DBHIP_OK;
 }
 
 int32_t dbhip_pq_chunk_decode_device(dbhip_pq_chunk* c, const uint8_t* chunk_dev, uint8_t* image_dev, void* out_values_dev,

@@ -228,6 +228,13 @@ struct dbhip_pq_chunk {
   void* d_ent_values = nullptr;
   uint32_t* d_rcnt = nullptr; uint32_t* d_ecnt = nullptr; uint64_t* d_roff = nullptr; uint64_t* d_eoff = nullptr; uint64_t* d_lblk = nullptr;
   uint64_t* d_lcounts = nullptr;
+  // DELTA_BYTE_ARRAY pages: their values, materialised by the last decode into one arena (buffer 1 of a String column); owned by the handle
+  // until dbhip_pq_chunk_take_arena hands it over, freed by the next decode or close otherwise
+  void* d_arena = nullptr;
+  int64_t arena_bytes = 0;
+  // data pages in DELTA_LENGTH_BYTE_ARRAY / DELTA_BYTE_ARRAY / BYTE_STREAM_SPLIT, of them DELTA_BYTE_ARRAY, and the u32 words of scratch their
+  // lengths take (counted by open_device: a batch without such pages does no per-page work for them)
+  int64_t n_ext = 0, n_dba = 0, ext_lens = 0;
 };
 
 namespace {

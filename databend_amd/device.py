@@ -47,6 +47,14 @@ class DeviceBuffer:
         self.ptr = p.value
 
     @classmethod
+    def adopt(cls, ptr, nbytes):
+        """take ownership of an allocation the library handed over (freed with dbhip_free like any other)"""
+        b = cls.__new__(cls)
+        b.nbytes = int(nbytes)
+        b.ptr = ptr
+        return b
+
+    @classmethod
     def from_numpy(cls, arr):
         arr = np.ascontiguousarray(arr)
         b = cls(arr.nbytes)
@@ -1947,6 +1955,19 @@ class ParquetChunk:
             return self.host
         return self.image_dev.to_numpy(np.uint8, self.info.image_bytes)
 
+    def take_arena(self):
+        """dbhip_pq_chunk_take_arena: the DELTA_BYTE_ARRAY values of the last decode (buffer 1 of a String column) as an owned
+        DeviceBuffer, or None when no page needed one"""
+        p, n = C.c_void_p(), C.c_int64()
+        check(lib().dbhip_pq_chunk_take_arena(self.h, C.byref(p), C.byref(n)))
+        return DeviceBuffer.adopt(p.value, n.value) if p.value else None
+
+    def _string_buffers(self, buf0):
+        """(device array of buffer pointers, buffers to keep alive) of a String column: [buf0] or [buf0, arena]"""
+        arena = self.take_arena()
+        keep = (buf0,) if arena is None else (buf0, arena)
+        return DeviceBuffer.from_numpy(np.array([b.ptr for b in keep], dtype=np.uint64)), keep
+
     def decode(self, stream=None):
         i = self.info
         chunk_dev = self.upload()
@@ -1966,10 +1987,12 @@ class ParquetChunk:
         else:
             check(lib().dbhip_pq_chunk_decode(self.h, C.c_void_p(chunk_dev.ptr), C.c_void_p(out.ptr),
                                               C.c_void_p(val.ptr) if val is not None else None, stream))
-        bufs = None
+        bufs, keep = None, (buf0,)
         if self.out_type == L.T_STRING:
-            bufs = DeviceBuffer.from_numpy(np.array([buf0.ptr], dtype=np.uint64))
-        return Column(self.out_type, i.num_values, out, val, self.precision, self.scale, buffers=bufs, keep=(buf0,))
+            bufs, keep = self._string_buffers(buf0)
+        col = Column(self.out_type, i.num_values, out, val, self.precision, self.scale, buffers=bufs, keep=keep)
+        col.n_buffers = len(keep) if bufs is not None else 0
+        return col
 
     def decode_list(self, stream=None):
         """dbhip_pq_chunk_decode_device_list -> (offsets numpy u64 [rows + 1], list validity numpy bool [rows] or None, element Column)"""
@@ -1987,8 +2010,9 @@ class ParquetChunk:
                                                       C.c_void_p(eval_.ptr) if eval_ is not None else None, C.byref(rows), C.byref(elems), C.byref(nl), stream))
         self.rows, self.elems, self.null_lists = rows.value, elems.value, nl.value
         buf0 = self.image_dev if self.image_dev is not None else chunk_dev
-        bufs = DeviceBuffer.from_numpy(np.array([buf0.ptr], dtype=np.uint64)) if self.out_type == L.T_STRING else None
-        col = Column(self.out_type, elems.value, out, eval_, self.precision, self.scale, buffers=bufs, keep=(buf0,))
+        bufs, keep = self._string_buffers(buf0) if self.out_type == L.T_STRING else (None, (buf0,))
+        col = Column(self.out_type, elems.value, out, eval_, self.precision, self.scale, buffers=bufs, keep=keep)
+        col.n_buffers = len(keep) if bufs is not None else 0
         lv = unpack_bits(lval.to_numpy(np.uint8, (rows.value + 7) // 8), rows.value) if lval is not None else None
         return offs.to_numpy(np.uint64, rows.value + 1), lv, col
 
@@ -2031,8 +2055,10 @@ class ParquetChunk:
                 continue
             pc.nulls = nulls[k]
             buf0 = pc.image_dev if pc.image_dev is not None else pc.chunk_dev
-            bufs = DeviceBuffer.from_numpy(np.array([buf0.ptr], dtype=np.uint64)) if pc.out_type == L.T_STRING else None
-            cols.append(Column(pc.out_type, pc.info.num_values, outs[k], vals[k], pc.precision, pc.scale, buffers=bufs, keep=(buf0,)))
+            bufs, keep = pc._string_buffers(buf0) if pc.out_type == L.T_STRING else (None, (buf0,))
+            col = Column(pc.out_type, pc.info.num_values, outs[k], vals[k], pc.precision, pc.scale, buffers=bufs, keep=keep)
+            col.n_buffers = len(keep) if bufs is not None else 0
+            cols.append(col)
         return cols
 
     def close(self):

@@ -58,6 +58,8 @@ inline void init(int device = 0) { check(dbhip_init(device)); }
 class DeviceBuffer {
  public:
   explicit DeviceBuffer(size_t bytes) : bytes_(bytes) { check(dbhip_alloc(bytes < 16 ? 16 : bytes + 16, &p_)); }
+  struct Adopt {};
+  DeviceBuffer(Adopt, void* p, size_t bytes) : p_(p), bytes_(bytes) {}   // an allocation the library handed over (freed with dbhip_free)
   ~DeviceBuffer() { if (p_) dbhip_free(p_); }
   DeviceBuffer(const DeviceBuffer&) = delete;
   DeviceBuffer& operator=(const DeviceBuffer&) = delete;
@@ -72,6 +74,7 @@ class DeviceBuffer {
 };
 using Buf = std::shared_ptr<DeviceBuffer>;
 inline Buf make_buf(size_t bytes) { return std::make_shared<DeviceBuffer>(bytes); }
+inline Buf adopt_buf(void* p, size_t bytes) { return std::make_shared<DeviceBuffer>(DeviceBuffer::Adopt{}, p, bytes); }
 
 // ---- types -----------------------------------------------------------------------------------
 struct DataType {
@@ -148,6 +151,7 @@ struct Column {
   Buf validity;   // LSB-first bits, NULL when the column is not nullable / has no NULLs
   Buf str_data;   // String: data buffer 0 (long strings)
   Buf str_ptrs;   // String: device array of device pointers to the data buffers
+  Buf str_arena;  // String: data buffer 1, or NULL (the DELTA_BYTE_ARRAY values a scan materialised: dbhip_pq_chunk_take_arena)
   bool is_const = false;  // BlockEntry::Const (block.rs): ONE stored value that stands for every row (e.g. a query vector)
 
   template <typename T>
@@ -257,7 +261,7 @@ struct Column {
     o.type = type.id; o.is_scalar = 0; o.data = data ? data->ptr() : nullptr;
     o.validity = validity ? (const uint8_t*)validity->ptr() : nullptr;
     o.buffers = str_ptrs ? (const void* const*)str_ptrs->ptr() : nullptr;
-    o.n_buffers = str_ptrs ? 1 : 0;
+    o.n_buffers = str_ptrs ? (str_arena ? 2 : 1) : 0;
     o.precision = type.precision; o.scale = type.scale;
     return o;
   }
@@ -848,7 +852,7 @@ inline Selection filter_select(const Column& predicate) {
 }
 
 inline Column take(const Column& c, const uint32_t* selp, int64_t k) {
-  Column r; r.type = c.type; r.len = k; r.str_data = c.str_data; r.str_ptrs = c.str_ptrs;
+  Column r; r.type = c.type; r.len = k; r.str_data = c.str_data; r.str_ptrs = c.str_ptrs; r.str_arena = c.str_arena;
   if (c.type.id == DBHIP_T_BOOL) {
     r.data = make_buf((size_t)(k + 63) / 64 * 8 + 8);
     check(dbhip_take_bitmap((const uint8_t*)c.data->ptr(), 0, selp, k, (uint8_t*)r.data->ptr(), nullptr));
@@ -2013,6 +2017,18 @@ inline std::optional<Column> column_chunk_to_column(const uint8_t* bytes, size_t
   return c;
 }
 
+// a device-mode String column's buffer table: buffer 0 the chunk / image, buffer 1 the arena of its DELTA_BYTE_ARRAY values (if any)
+inline void set_string_buffers(Column& c, const Buf& buf0, dbhip_pq_chunk* h) {
+  void* arena = nullptr;
+  int64_t arena_bytes = 0;
+  check(dbhip_pq_chunk_take_arena(h, &arena, &arena_bytes));
+  c.str_data = buf0;
+  c.str_arena = arena ? adopt_buf(arena, (size_t)arena_bytes) : nullptr;
+  void* p[2] = {buf0->ptr(), arena};
+  c.str_ptrs = make_buf(sizeof(p));
+  c.str_ptrs->upload(p, sizeof(p));
+}
+
 // ---- the same for a whole block, device mode (round 5): every leaf's page headers are read on the host, the chunks go to HBM AS
 // STORED, and ONE dbhip_pq_chunks_decode_device call decompresses (ZSTD / LZ4 / Snappy) and decodes all of them. A leaf the library
 // declines (std::nullopt in the result) stays with the arrow-rs reader; a malformed chunk raises like any decode error.
@@ -2064,12 +2080,8 @@ inline std::vector<std::optional<Column>> column_chunks_to_columns(const std::ve
     if (status[k] == DBHIP_ERR_UNSUPPORTED) continue;     // (a form found on the device that stays with the CPU reader)
     if (status[k] != DBHIP_OK) check(rc);
     Column& c = cols[k];
-    if (field_types[which[k]].id == DBHIP_T_STRING) {      // views point into the decompressed image (or the chunk itself)
-      c.str_data = image_dev[k] ? image_dev[k] : chunk_dev[k];
-      void* p = c.str_data->ptr();
-      c.str_ptrs = make_buf(sizeof(void*));
-      c.str_ptrs->upload(&p, sizeof(void*));
-    }
+    if (field_types[which[k]].id == DBHIP_T_STRING)       // views point into the decompressed image (or the chunk itself) and the arena
+      set_string_buffers(c, image_dev[k] ? image_dev[k] : chunk_dev[k], h[k]);
     out[which[k]] = std::move(c);
   }
   return out;
@@ -2113,12 +2125,7 @@ inline std::optional<ListColumn> list_chunk_to_column(const uint8_t* bytes, size
     L.list_valid.resize((size_t)rows);
     for (int64_t r = 0; r < rows; ++r) L.list_valid[(size_t)r] = (bits[(size_t)r >> 3] >> (r & 7)) & 1;
   }
-  if (element_type.id == DBHIP_T_STRING) {
-    c.str_data = image ? image : chunk;
-    void* p = c.str_data->ptr();
-    c.str_ptrs = make_buf(sizeof(void*));
-    c.str_ptrs->upload(&p, sizeof(void*));
-  }
+  if (element_type.id == DBHIP_T_STRING) set_string_buffers(c, image ? image : chunk, h);
   return L;
 }
 

@@ -40,7 +40,8 @@
 extern "C" {
 #endif
 
-#define DBHIP_ABI_VERSION 6   /* 6 (round 6): pipelined fused aggregation (dbhip_groupby_set_pipelined / dbhip_groupby_checkpoint); 5 (round 5): ZSTD on the device, batched chunk decode (dbhip_pq_chunks_decode_device); 4 (round 4): block scatter / concat, exchange and plan calls, device-mode scan, cancellation, row-wise vector distance */
+#define DBHIP_ABI_VERSION 6   /* 6 (round 6): pipelined fused aggregation (dbhip_groupby_set_pipelined / dbhip_groupby_checkpoint), and (backward
+                                 compatible, same version) DELTA_(LENGTH_)BYTE_ARRAY / BYTE_STREAM_SPLIT on the device with dbhip_pq_chunk_take_arena; 5 (round 5): ZSTD on the device, batched chunk decode (dbhip_pq_chunks_decode_device); 4 (round 4): block scatter / concat, exchange and plan calls, device-mode scan, cancellation, row-wise vector distance */
 
 /* ---- status codes ------------------------------------------------------- */
 enum {
@@ -964,11 +965,17 @@ int32_t dbhip_pq_chunk_decode(dbhip_pq_chunk* c, const uint8_t* chunk_dev, void*
  * ZSTD, the reference's default TableCompression: Huffman literals + FSE sequences walked on the GPU, frames with a dictionary
  * id are DBHIP_ERR_UNSUPPORTED; SNAPPY / LZ4_RAW), walks the run headers of the RLE / bit-packed hybrid streams (definition
  * levels, dictionary indices, RLE booleans), the length prefixes of PLAIN BYTE_ARRAY pages and DELTA_BINARY_PACKED blocks
- * (INT32 / INT64) on the GPU, from the HBM copy of the chunk AS STORED. Same type pairs, same output layout as open / decode.
+ * (INT32 / INT64) on the GPU, from the HBM copy of the chunk AS STORED. Value encodings of data pages: PLAIN, PLAIN_DICTIONARY /
+ * RLE_DICTIONARY, RLE (BOOLEAN), DELTA_BINARY_PACKED (INT32, INT64), DELTA_LENGTH_BYTE_ARRAY (BYTE_ARRAY), DELTA_BYTE_ARRAY
+ * (BYTE_ARRAY, FIXED_LEN_BYTE_ARRAY), BYTE_STREAM_SPLIT (FLOAT, DOUBLE, INT32, INT64, FIXED_LEN_BYTE_ARRAY); any other pair is
+ * DBHIP_ERR_UNSUPPORTED at open. Same type pairs, same output layout as open / decode. DELTA_BYTE_ARRAY values are materialised
+ * into an arena (buffer 1 of a String column: dbhip_pq_chunk_take_arena), sized on the device: a batch that holds such pages reads
+ * the sizes back once more before the values are written (and a chunk whose arena would reach 4 GiB is DBHIP_ERR_UNSUPPORTED).
  *   chunk_dev    the chunk as stored (the bytes given to open_device), 16-byte aligned, readable up to the next 16-byte
  *                boundary past its end
  *   image_dev    compressed chunks: info.image_bytes bytes, 16-byte aligned, caller-owned — receives the decompressed pages;
- *                DBHIP_T_STRING views point into it (it is buffer 0 of the column; UNCOMPRESSED chunks: chunk_dev is, pass NULL)
+ *                DBHIP_T_STRING views point into it (it is buffer 0 of the column; UNCOMPRESSED chunks: chunk_dev is, pass NULL);
+ *                the views of DELTA_BYTE_ARRAY values point into the chunk's arena, buffer 1 (dbhip_pq_chunk_take_arena)
  *   info.num_nulls is -1 when the page headers do not tell (v1 pages of a nullable column); out_nulls_host (may be NULL) gets
  *   the count. Nothing about the payload is validated on the host, so the device checks every access against the page, the
  *   dictionary and the output; decode_device synchronises `stream` and returns DBHIP_ERR_INVALID for a chunk that fails a check. */
@@ -981,7 +988,8 @@ int32_t dbhip_pq_chunk_decode_device(dbhip_pq_chunk* c, const uint8_t* chunk_dev
                                      void* stream);
 /* MANY chunks, one launch set (what a scan does: the column chunks of a block — or of several blocks — together): the pages of all
  * chunks are decompressed by ONE launch per codec family (ZSTD; SNAPPY + LZ4_RAW), their levels / dictionaries / values by one
- * launch each over all data pages, and the verdicts and null counts come back in one read-back. Arrays of n_chunks entries, as the
+ * launch each over all data pages, and the verdicts and null counts come back in one read-back (two when a chunk of the batch has
+ * DELTA_BYTE_ARRAY pages: their sizes come back first; each such chunk gets its own arena). Arrays of n_chunks entries, as the
  * arguments of dbhip_pq_chunk_decode_device (image_dev[i] / out_validity_dev[i] NULL where that call takes NULL);
  * out_nulls_host / out_status_host may be NULL. A chunk that fails its device checks gets its own status in out_status_host[i]
  * (the others are decoded); the call returns the first such status. Handles must be distinct. */
@@ -1005,6 +1013,12 @@ int32_t dbhip_pq_chunk_open_device_list(const uint8_t* chunk_host, int64_t chunk
 int32_t dbhip_pq_chunk_decode_device_list(dbhip_pq_chunk* c, const uint8_t* chunk_dev, uint8_t* image_dev, uint64_t* out_offsets_dev,
                                           uint8_t* out_list_validity_dev, void* out_values_dev, uint8_t* out_elem_validity_dev,
                                           int64_t* out_rows_host, int64_t* out_elems_host, int64_t* out_null_lists_host, void* stream);
+/* DELTA_BYTE_ARRAY pages (device mode): their values exist nowhere back to back, so decode_device / decode_device_list (and
+ * chunks_decode_device) materialise them into one ARENA per chunk, a device allocation of the library; the long views of such values
+ * point into it as buffer 1 of the column (buffer 0 stays the chunk / the image). take_arena hands the caller the arena of the last
+ * decode of `c` that made one: *out_dev_ptr_host / *out_bytes_host, NULL / 0 when no page needed one (and on a second call). The
+ * caller then owns it and frees it with dbhip_free; an arena that is not taken is freed by the next decode of `c` or by close. */
+int32_t dbhip_pq_chunk_take_arena(dbhip_pq_chunk* c, void** out_dev_ptr_host, int64_t* out_bytes_host);
 int32_t dbhip_pq_chunk_close(dbhip_pq_chunk* c);
 
 /* ---------------------------------------------------------------------------------------------------------------------
