@@ -155,6 +155,22 @@ pub struct dbhip_pq_info {
     pub image_bytes: i64,
 }
 
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct dbhip_pq_node {
+    pub kind: i32,
+    pub nullable: i32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct dbhip_pq_node_out {
+    pub offsets_dev: *mut u64,
+    pub validity_dev: *mut u8,
+    pub items: i64,
+    pub nulls: i64,
+}
+
 extern "C" {
     pub fn dbhip_abi_version() -> i32;
     pub fn dbhip_init(device: i32) -> i32;
@@ -296,6 +312,8 @@ extern "C" {
     pub fn dbhip_pq_chunks_decode_device(chunks: *const *mut dbhip_pq_chunk, n_chunks: i32, chunk_dev: *const *const u8, image_dev: *const *mut u8, out_values_dev: *const *mut c_void, out_validity_dev: *const *mut u8, out_nulls_host: *mut i64, out_status_host: *mut i32, stream: *mut c_void) -> i32;
     pub fn dbhip_pq_chunk_open_device_list(chunk_host: *const u8, chunk_len: i64, codec: i32, physical_type: i32, type_length: i32, list_nullable: i32, element_nullable: i32, out_type: i32, out_host: *mut *mut dbhip_pq_chunk, info_host: *mut dbhip_pq_info) -> i32;
     pub fn dbhip_pq_chunk_decode_device_list(c: *mut dbhip_pq_chunk, chunk_dev: *const u8, image_dev: *mut u8, out_offsets_dev: *mut u64, out_list_validity_dev: *mut u8, out_values_dev: *mut c_void, out_elem_validity_dev: *mut u8, out_rows_host: *mut i64, out_elems_host: *mut i64, out_null_lists_host: *mut i64, stream: *mut c_void) -> i32;
+    pub fn dbhip_pq_chunk_open_device_nested(chunk_host: *const u8, chunk_len: i64, codec: i32, physical_type: i32, type_length: i32, path: *const dbhip_pq_node, n_nodes: i32, leaf_nullable: i32, out_type: i32, out_host: *mut *mut dbhip_pq_chunk, info_host: *mut dbhip_pq_info) -> i32;
+    pub fn dbhip_pq_chunk_decode_device_nested(c: *mut dbhip_pq_chunk, chunk_dev: *const u8, image_dev: *mut u8, nodes_host: *mut dbhip_pq_node_out, out_values_dev: *mut c_void, out_rows_host: *mut i64, stream: *mut c_void) -> i32;
     pub fn dbhip_pq_chunk_take_arena(c: *mut dbhip_pq_chunk, out_dev_ptr_host: *mut *mut c_void, out_bytes_host: *mut i64) -> i32;
     pub fn dbhip_pq_chunk_close(c: *mut dbhip_pq_chunk) -> i32;
     pub fn dbhip_hnsw_build(vectors_dev: *const f32, n: i64, dim: i32, distance: i32, m: i32, ef_construct: i32, seed: u64, out: *mut *mut dbhip_hnsw, stream: *mut c_void) -> i32;

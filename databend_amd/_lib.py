@@ -55,6 +55,19 @@ class PqInfo(C.Structure):
                 ("image_bytes", C.c_int64)]
 
 
+class PqNode(C.Structure):
+    """dbhip_pq_node"""
+    _fields_ = [("kind", C.c_int32), ("nullable", C.c_int32)]
+
+
+class PqNodeOut(C.Structure):
+    """dbhip_pq_node_out"""
+    _fields_ = [("offsets_dev", C.c_void_p), ("validity_dev", C.c_void_p), ("items", C.c_int64), ("nulls", C.c_int64)]
+
+
+# dbhip_pq_node.kind
+PQ_LIST, PQ_STRUCT = 1, 2
+
 # parquet.thrift Type numbers
 PQ_BOOLEAN, PQ_INT32, PQ_INT64, PQ_INT96, PQ_FLOAT, PQ_DOUBLE, PQ_BYTE_ARRAY, PQ_FLBA = range(8)
 # parquet.thrift CompressionCodec numbers the library decodes
@@ -97,7 +110,7 @@ SYMBOLS = [
     "dbhip_hnsw_encoded", "dbhip_hnsw_meta", "dbhip_hnsw_destroy",
     "dbhip_pq_chunk_open", "dbhip_pq_chunk_validity", "dbhip_pq_chunk_image", "dbhip_pq_chunk_decode", "dbhip_pq_chunk_close",
     "dbhip_pq_chunk_open_device", "dbhip_pq_chunk_decode_device", "dbhip_pq_chunks_decode_device", "dbhip_pq_chunk_open_device_list", "dbhip_pq_chunk_decode_device_list",
-    "dbhip_pq_chunk_take_arena",
+    "dbhip_pq_chunk_take_arena", "dbhip_pq_chunk_open_device_nested", "dbhip_pq_chunk_decode_device_nested",
     "dbhip_scatter_columns", "dbhip_concat_columns", "dbhip_comm_create_loopback", "dbhip_exchange_begin", "dbhip_shuffle_exchange_begin", "dbhip_sort_exchange_begin", "dbhip_exchange_finish", "dbhip_exchange_string_bytes", "dbhip_exchange_finish_strings", "dbhip_exchange_destroy", "dbhip_vec_topk_allgather",
     # diagnostics and test hooks (declared in the header's last section)
     "dbhip_groupby_debug_set_hash_mask", "dbhip_groupby_debug_set_partition_bits", "dbhip_groupby_debug_set_compact", "dbhip_join_binary_debug_set_hash_mask",

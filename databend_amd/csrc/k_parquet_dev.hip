@@ -27,6 +27,9 @@
 //   dv_inflate_zstd2_kernel  ZSTD (the reference's DEFAULT codec, table_compression.rs:27-28): two waves per page — one walks the frame
 //                       with zstd_core.h (Huffman literals by up to four lanes, FSE sequences from a look-ahead window in registers) and
 //                       queues commands, the other replays them through a 4 KiB LDS ring + far references from the image: dv_wave.h.
+// Nested leaves (dbhip_pq_chunk_open_device_nested): dv_levels_kernel<true> leaves every level entry's (r, d) as bytes, pq_nest_count_kernel
+// counts the slots each 32-entry word opens in every index space, one scan per space, and pq_nest_finish_kernel writes every node's offsets and
+// validity and moves the leaf values to their slots.
 // dbhip_pq_chunks_decode_device decodes MANY chunks with one launch set (one inflate launch per codec family over all their pages, one
 // levels / scan / dictionary / values launch over all their data pages, one read-back): a scan keeps dozens of column chunks in flight.
 #include "pq_common.h"
@@ -43,6 +46,9 @@ __host__ __device__ __forceinline__ bool dv_ext_enc(uint32_t e) {
   return e == ENC_DELTA_LENGTH_BYTE_ARRAY || e == ENC_DELTA_BYTE_ARRAY || e == ENC_BYTE_STREAM_SPLIT;
 }
 enum { CODEC_NONE = 0, CODEC_SNAPPY = 1, CODEC_ZSTD = 6, CODEC_LZ4_RAW = 7 };
+enum { PQ_NODE_LIST = 1, PQ_NODE_STRUCT = 2 };   // dbhip_pq_node.kind
+// bits of a level whose largest value is v (parquet's bit width of the level streams)
+inline uint32_t bit_width_u32(uint32_t v) { uint32_t b = 0; for (; v; v >>= 1) ++b; return b; }
 
 __device__ __forceinline__ void dv_fail(uint32_t* ctl, uint32_t code) { atomicCAS(&ctl[0], 0u, code); }
 
@@ -321,7 +327,57 @@ struct DvChunkD {
   uint32_t* isrep;
   uint32_t* iselem;
   uint32_t* lvalid;
+  // nested leaves: bit width of the repetition levels (List columns: 1; 0 = the leaf has no LIST above it, v1 pages carry no repetition
+  // stream), the largest repetition level, and the per-entry level bytes dv_levels_kernel<true> writes (List columns: the bitmaps above)
+  uint32_t rw, rmax;
+  uint8_t* lrep;
+  uint8_t* ldef;
 };
+
+// the n bytes at p := v, by all `nthr` threads (the aligned middle as words)
+__device__ __forceinline__ void dv_fill_bytes(uint8_t* __restrict__ p, uint32_t n, uint8_t v, uint32_t tid, uint32_t nthr) {
+  const uint32_t a = (4u - (uint32_t)((uintptr_t)p & 3u)) & 3u, head = a < n ? a : n;
+  if (tid < head) p[tid] = v;
+  const uint32_t nw = (n - head) >> 2;
+  uint32_t* __restrict__ pw = (uint32_t*)(p + head);
+  const uint32_t v4 = (uint32_t)v * 0x01010101u;
+  for (uint32_t i = tid; i < nw; i += nthr) pw[i] = v4;
+  const uint32_t done = head + 4 * nw;
+  if (tid < n - done) p[done + tid] = v;
+}
+
+// nested leaves: `n` levels from entry dst0 on — packed at width bw (src) or a run of `run` — as one byte per entry into lev; with a
+// bitmap (the definition levels), also the entries whose level is vmax (= carry a value), of which this thread's share is returned.
+// *bad: a level above vmax. Called by all `nthr` threads (whole waves); packed levels one entry per lane, as dv_put_def.
+template <bool LDS = false>
+__device__ __forceinline__ uint32_t dv_put_lev(uint8_t* __restrict__ lev, uint32_t* __restrict__ bitmap, uint32_t vmax, uint32_t bw, uint64_t dst0, uint32_t n,
+                                               const uint8_t* __restrict__ src, uint32_t run, uint32_t tid, uint32_t nthr, bool* bad) {
+  if (n == 0) return 0;
+  if (!src) {
+    if (run > vmax) *bad = true;
+    dv_fill_bytes(lev + dst0, n, (uint8_t)run, tid, nthr);
+    return bitmap && run == vmax ? dv_put_bits(bitmap, dst0, n, nullptr, tid, nthr) : 0u;
+  }
+  uint32_t ones = 0;
+  const uint32_t lane = tid & 63u;
+  for (uint32_t base = tid & ~63u; base < n; base += nthr) {
+    const uint32_t x = base + lane;
+    const bool in = x < n;
+    const uint32_t v = in ? lv_extract_bits<LDS>(src, x, (int)bw) : 0u;
+    if (in && v > vmax) *bad = true;
+    if (in) lev[dst0 + x] = (uint8_t)v;
+    if (!bitmap) continue;
+    const uint64_t mv = __ballot(in && v == vmax);
+    if (lane < 3) {
+      const uint64_t p0 = dst0 + base;
+      const uint32_t sh = (uint32_t)(p0 & 31);
+      const uint32_t bv = lane == 0 ? (uint32_t)(mv << sh) : lane == 1 ? (uint32_t)(mv >> (32 - sh)) : (sh ? (uint32_t)(mv >> (64 - sh)) : 0u);
+      if (bv) atomicOr(&bitmap[(p0 >> 5) + lane], bv);
+      if (lane == 0) ones += (uint32_t)__popcll(mv);
+    }
+  }
+  return ones;
+}
 
 // definition levels of `n` entries from dst0 on — packed at width dw (src) or a run of `run` — into the three entry bitmaps; returns this
 // thread's share of the entries that carry a value. *bad: a level above the column's maximum. Called by all `nthr` threads (whole waves).
@@ -380,7 +436,9 @@ __device__ __forceinline__ uint32_t dv_put_def(const DvChunkD& C, uint64_t dst0,
 // image every hop is an HBM / L2 round trip (plus one for the run's payload): 9.7 ms for the 300 pages of a 6 M-row List<Int64> chunk,
 // ~1 us per run. With `lds_bytes` of dynamic LDS (batches that hold a List chunk) the workgroup first copies both streams into LDS — they
 // are contiguous in the page, 25-35 KB for a 1 MiB page — and walks them there; streams that do not fit are walked in place as before.
+// NEST: the instantiation for a nested leaf (dv_put_lev; a batch that holds one is that chunk alone); flat and List chunks keep the other.
 constexpr uint32_t LV_LDS = 40960;
+template <bool NEST>
 __global__ __launch_bounds__(256) void dv_levels_kernel(const DvChunkD* __restrict__ cds, const uint2* __restrict__ map, uint32_t lds_bytes) {
   extern __shared__ __align__(16) uint8_t lv_lds[];
   __shared__ uint32_t sh4[4];
@@ -398,19 +456,20 @@ __global__ __launch_bounds__(256) void dv_levels_kernel(const DvChunkD* __restri
   uint32_t len, vo;
   const uint8_t* stream;
   if (C.ldw) {
-    // a List column's page: repetition levels (width 1), then definition levels (width ldw), then the values
+    // a List column's / nested leaf's page: repetition levels (width rw), then definition levels (width ldw), then the values
     const uint8_t* rep;
     uint32_t rlen;
     bool ok = true;
     if (P.type == PG_DATA) {
-      ok = P.uncomp_len >= 8;
-      rlen = ok ? (uint32_t)load_le(s, 4) : 0;
-      ok = ok && rlen <= P.uncomp_len - 8;
-      rep = s + 4;
-      len = ok ? (uint32_t)load_le(s + 4 + rlen, 4) : 0;
-      ok = ok && len <= P.uncomp_len - 8 - rlen;
-      stream = s + 8 + rlen;
-      vo = 8 + rlen + len;
+      const uint32_t rh = !NEST || C.rw ? 4u : 0u;     // (a nested leaf without a LIST above it: no repetition stream)
+      ok = P.uncomp_len >= rh + 4;
+      rlen = ok && rh ? (uint32_t)load_le(s, 4) : 0;
+      ok = ok && rlen <= P.uncomp_len - rh - 4;
+      rep = s + rh;
+      len = ok ? (uint32_t)load_le(s + rh + rlen, 4) : 0;
+      ok = ok && len <= P.uncomp_len - rh - 4 - rlen;
+      stream = s + rh + 4 + rlen;
+      vo = rh + 4 + rlen + len;
     } else {
       rlen = P.rep_len; rep = s;              // (the host checked rep_len <= lev_len <= uncomp_len)
       len = P.lev_len - P.rep_len; stream = s + rlen;
@@ -438,30 +497,54 @@ __global__ __launch_bounds__(256) void dv_levels_kernel(const DvChunkD* __restri
         W.open(lv_lds + k, lv_lds + lds_bytes, tid);
         const uint8_t* base = lv_lds + k;
         const uint32_t dat = (uint32_t)(stream - rep);
-        ok = dv_walk_hybrid_wave(
-            W, base, 0, rlen, 1, P.num_values,
-            [&](uint32_t first, uint32_t n, uint32_t v) { if (v == 1) (void)dv_put_bits(C.isrep, r0 + first, n, nullptr, tid, 64); },
-            [&](uint32_t first, uint32_t n, const uint8_t* src) { (void)dv_put_bits<true>(C.isrep, r0 + first, n, src, tid, 64); });
+        ok = (NEST && C.rw == 0) || dv_walk_hybrid_wave(
+            W, base, 0, rlen, NEST ? (int)C.rw : 1, P.num_values,
+            [&](uint32_t first, uint32_t n, uint32_t v) {
+              if constexpr (NEST) (void)dv_put_lev(C.lrep, nullptr, C.rmax, C.rw, r0 + first, n, nullptr, v, tid, 64, &bad);
+              else if (v == 1) (void)dv_put_bits(C.isrep, r0 + first, n, nullptr, tid, 64);
+            },
+            [&](uint32_t first, uint32_t n, const uint8_t* src) {
+              if constexpr (NEST) (void)dv_put_lev<true>(C.lrep, nullptr, C.rmax, C.rw, r0 + first, n, src, 0, tid, 64, &bad);
+              else (void)dv_put_bits<true>(C.isrep, r0 + first, n, src, tid, 64);
+            });
         uint32_t mine = 0;
         ok = ok && dv_walk_hybrid_wave(
             W, base, dat, len, (int)C.ldw, P.num_values,
-            [&](uint32_t first, uint32_t n, uint32_t v) { mine += dv_put_def(C, r0 + first, n, nullptr, v, tid, 64, &bad); },
-            [&](uint32_t first, uint32_t n, const uint8_t* src) { mine += dv_put_def<true>(C, r0 + first, n, src, 0, tid, 64, &bad); });
+            [&](uint32_t first, uint32_t n, uint32_t v) {
+              if constexpr (NEST) mine += dv_put_lev(C.ldef, C.bitmap, C.lmax, C.ldw, r0 + first, n, nullptr, v, tid, 64, &bad);
+              else mine += dv_put_def(C, r0 + first, n, nullptr, v, tid, 64, &bad);
+            },
+            [&](uint32_t first, uint32_t n, const uint8_t* src) {
+              if constexpr (NEST) mine += dv_put_lev<true>(C.ldef, C.bitmap, C.lmax, C.ldw, r0 + first, n, src, 0, tid, 64, &bad);
+              else mine += dv_put_def<true>(C, r0 + first, n, src, 0, tid, 64, &bad);
+            });
         for (int dd = 32; dd >= 1; dd >>= 1) mine += __shfl_xor(mine, dd, 64);
         if (!ok || __ballot(bad) != 0) { dv_fail(ctl, DV_CORRUPT); ok = false; }
         if (tid == 0) { nn[d] = ok ? mine : 0; voff[d] = ok ? vo : P.uncomp_len; }
         return;
       }
     }
-    ok = dv_walk_hybrid(
-        rep, rlen, 1, P.num_values,
-        [&](uint32_t first, uint32_t n, uint32_t v) { if (v == 1) (void)dv_put_bits(C.isrep, r0 + first, n, nullptr, tid, 256); },
-        [&](uint32_t first, uint32_t n, const uint8_t* src) { (void)dv_put_bits(C.isrep, r0 + first, n, src, tid, 256); });
+    ok = (NEST && C.rw == 0) || dv_walk_hybrid(
+        rep, rlen, NEST ? (int)C.rw : 1, P.num_values,
+        [&](uint32_t first, uint32_t n, uint32_t v) {
+          if constexpr (NEST) (void)dv_put_lev(C.lrep, nullptr, C.rmax, C.rw, r0 + first, n, nullptr, v, tid, 256, &bad);
+          else if (v == 1) (void)dv_put_bits(C.isrep, r0 + first, n, nullptr, tid, 256);
+        },
+        [&](uint32_t first, uint32_t n, const uint8_t* src) {
+          if constexpr (NEST) (void)dv_put_lev(C.lrep, nullptr, C.rmax, C.rw, r0 + first, n, src, 0, tid, 256, &bad);
+          else (void)dv_put_bits(C.isrep, r0 + first, n, src, tid, 256);
+        });
     uint32_t mine = 0;
     ok = ok && dv_walk_hybrid(
         stream, len, (int)C.ldw, P.num_values,
-        [&](uint32_t first, uint32_t n, uint32_t v) { mine += dv_put_def(C, r0 + first, n, nullptr, v, tid, 256, &bad); },
-        [&](uint32_t first, uint32_t n, const uint8_t* src) { mine += dv_put_def(C, r0 + first, n, src, 0, tid, 256, &bad); });
+        [&](uint32_t first, uint32_t n, uint32_t v) {
+          if constexpr (NEST) mine += dv_put_lev(C.ldef, C.bitmap, C.lmax, C.ldw, r0 + first, n, nullptr, v, tid, 256, &bad);
+          else mine += dv_put_def(C, r0 + first, n, nullptr, v, tid, 256, &bad);
+        },
+        [&](uint32_t first, uint32_t n, const uint8_t* src) {
+          if constexpr (NEST) mine += dv_put_lev(C.ldef, C.bitmap, C.lmax, C.ldw, r0 + first, n, src, 0, tid, 256, &bad);
+          else mine += dv_put_def(C, r0 + first, n, src, 0, tid, 256, &bad);
+        });
     const uint32_t total = dv_block_sum(mine, sh4);
     if (!ok || __syncthreads_or(bad ? 1 : 0)) { dv_fail(ctl, DV_CORRUPT); ok = false; }
     if (tid == 0) { nn[d] = ok ? total : 0; voff[d] = ok ? vo : P.uncomp_len; }
@@ -1040,17 +1123,22 @@ extern "C" {
 }  // extern "C"
 namespace {
 // list_mode: a List<primitive> leaf (one repeated ancestor): max_def_level = list_nullable + 1 + element_nullable, max_rep_level = 1
+// nest_rep >= 0: a nested leaf (dbhip_pq_chunk_open_device_nested) with that many repeated levels; max_def_level is then the leaf's
 int32_t open_device_impl(const uint8_t* chunk_host, int64_t chunk_len, int32_t codec, int32_t physical_type, int32_t type_length,
                          int32_t max_def_level, int32_t max_rep_level, int32_t out_type, bool list_mode, int32_t list_nullable, int32_t elem_nullable,
-                         dbhip_pq_chunk** out_host, dbhip_pq_info* info_host) {
+                         dbhip_pq_chunk** out_host, dbhip_pq_info* info_host, int32_t nest_rep = -1) {
+  const bool nested = nest_rep >= 0;
+  const bool lv_mode = list_mode || nested;     // rows = level entries, the leaf a nullable column over them
   DBHIP_REQUIRE(chunk_host && out_host && chunk_len >= 0, "dbhip_pq_chunk_open_device: NULL argument");
   *out_host = nullptr;
   if (codec != CODEC_NONE && codec != CODEC_SNAPPY && codec != CODEC_LZ4_RAW && codec != CODEC_ZSTD)
     return dv_unsupported("compression codec other than UNCOMPRESSED / SNAPPY / ZSTD / LZ4_RAW");
-  if (!list_mode && (max_rep_level != 0 || max_def_level < 0 || max_def_level > 1))
+  if (!lv_mode && (max_rep_level != 0 || max_def_level < 0 || max_def_level > 1))
     return dv_unsupported("nested column (repetition / definition level > 1; List<primitive>: dbhip_pq_chunk_open_device_list)");
   const int32_t list_max_def = list_mode ? max_def_level : 0;
+  const int32_t nest_max_def = nested ? max_def_level : 0;
   if (list_mode) max_def_level = 1;   // (for the flat pipeline the leaf is a nullable column over the level entries)
+  if (nested) max_def_level = max_def_level > 0 ? 1 : 0;   // (no levels at all: every entry is a row with a value)
   if (chunk_len >= (1LL << 32)) return dv_unsupported("column chunk of 4 GiB or more");
   if (!type_pair_ok(physical_type, type_length, out_type)) {
     set_error("dbhip_pq_chunk_open_device: physical type %d (length %d) cannot be decoded into dbhip type %d", physical_type, type_length, out_type);
@@ -1061,6 +1149,7 @@ int32_t open_device_impl(const uint8_t* chunk_host, int64_t chunk_len, int32_t c
   c->device_mode = true; c->codec = codec;
   c->physical = physical_type; c->type_length = type_length; c->max_def = max_def_level; c->out_type = out_type;
   c->list = list_mode; c->list_nullable = list_nullable; c->elem_nullable = elem_nullable; c->list_max_def = list_max_def;
+  c->nested = nested; c->n_lists = nested ? nest_rep : 0; c->nest_max_def = nest_max_def;
   c->chunk_len = chunk_len; c->rows = 0; c->nulls = -1; c->nonnull = 0; c->n_pages = 0;
   c->dict_n = -1; c->dict_off = 0; c->dict_bytes = 0;
   c->d_valid = nullptr; c->d_val = nullptr; c->d_str_off = nullptr; c->d_dict_str_off = nullptr; c->d_dict = nullptr; c->d_dense = nullptr;
@@ -1085,7 +1174,7 @@ int32_t open_device_impl(const uint8_t* chunk_host, int64_t chunk_len, int32_t c
       if (h.num_values < 0) { rc = dv_malformed("page without num_values"); break; }
       P.num_values = (uint32_t)h.num_values;
       if (h.type == PG_DATA_V2) {
-        if (h.rep_len != 0 && !list_mode) { rc = dv_unsupported("repetition levels"); break; }
+        if (h.rep_len != 0 && !list_mode && !(nested && nest_rep > 0)) { rc = nested ? dv_malformed("repetition levels in a leaf without a LIST") : dv_unsupported("repetition levels"); break; }
         if (h.def_len < 0 || h.rep_len < 0) { rc = dv_malformed("level byte length"); break; }
         P.rep_len = (uint32_t)h.rep_len;
         P.lev_len = (uint32_t)h.def_len + (uint32_t)h.rep_len;
@@ -1131,9 +1220,10 @@ int32_t open_device_impl(const uint8_t* chunk_host, int64_t chunk_len, int32_t c
         // List mode, v1 pages: dv_levels_kernel reads BOTH level streams as <4-byte length><RLE / bit-packed hybrid runs>; a legacy
         // BIT_PACKED stream (no length prefix) would be read as a length and runs
         if (list_mode && h.type == PG_DATA && (h.def_enc != ENC_RLE || h.rep_enc != ENC_RLE)) { rc = dv_unsupported("List column: definition / repetition levels not RLE encoded"); break; }
+        if (nested && h.type == PG_DATA && nest_rep > 0 && h.rep_enc != ENC_RLE) { rc = dv_unsupported("nested leaf: repetition levels not RLE encoded"); break; }
         if ((uint64_t)c->rows + (uint64_t)P.num_values >= 0xFFFFFFF0ULL) { rc = dv_unsupported("more than 2^32 rows in one chunk"); break; }
         P.row_start = (uint64_t)c->rows;
-        if (!(h.type == PG_DATA_V2 && h.num_nulls == 0) || list_mode) all_v2_no_nulls = false;
+        if (!(h.type == PG_DATA_V2 && h.num_nulls == 0) || lv_mode) all_v2_no_nulls = false;
         if (dv_ext_enc((uint32_t)e)) {
           c->n_ext += 1;
           if (e == ENC_DELTA_BYTE_ARRAY) { c->n_dba += 1; c->ext_lens += 2 * (int64_t)P.num_values; }
@@ -1192,6 +1282,37 @@ int32_t dbhip_pq_chunk_open_device_list(const uint8_t* chunk_host, int64_t chunk
   return rc;
 }
 
+int32_t dbhip_pq_chunk_open_device_nested(const uint8_t* chunk_host, int64_t chunk_len, int32_t codec, int32_t physical_type, int32_t type_length,
+                                          const dbhip_pq_node* path, int32_t n_nodes, int32_t leaf_nullable, int32_t out_type, dbhip_pq_chunk** out_host,
+                                          dbhip_pq_info* info_host) {
+  DBHIP_REQUIRE(out_host, "dbhip_pq_chunk_open_device_nested: NULL argument");
+  *out_host = nullptr;
+  DBHIP_REQUIRE(path, "dbhip_pq_chunk_open_device_nested: NULL path");
+  DBHIP_REQUIRE(leaf_nullable == 0 || leaf_nullable == 1, "dbhip_pq_chunk_open_device_nested: leaf_nullable is 0 / 1");
+  if (n_nodes < 1 || n_nodes > 8) {
+    set_error("dbhip_pq_chunk_open_device_nested: %d path nodes (1 .. 8 are decoded)", n_nodes);
+    return DBHIP_ERR_UNSUPPORTED;
+  }
+  int32_t lists = 0, max_def = leaf_nullable;
+  for (int32_t j = 0; j < n_nodes; ++j) {
+    DBHIP_REQUIRE(path[j].kind == PQ_NODE_LIST || path[j].kind == PQ_NODE_STRUCT, "dbhip_pq_chunk_open_device_nested: a node kind is LIST (1) or STRUCT (2)");
+    DBHIP_REQUIRE(path[j].nullable == 0 || path[j].nullable == 1, "dbhip_pq_chunk_open_device_nested: node nullability is 0 / 1");
+    lists += path[j].kind == PQ_NODE_LIST;
+    max_def += path[j].nullable + (path[j].kind == PQ_NODE_LIST);
+  }
+  if (lists > 4) {
+    set_error("dbhip_pq_chunk_open_device_nested: %d LIST nodes (at most 4 repeated levels are decoded)", lists);
+    return DBHIP_ERR_UNSUPPORTED;
+  }
+  const int32_t rc = open_device_impl(chunk_host, chunk_len, codec, physical_type, type_length, max_def, lists, out_type, false, 0, 0, out_host, info_host, lists);
+  if (rc != DBHIP_OK) return rc;
+  dbhip_pq_chunk* c = *out_host;
+  c->n_nodes = n_nodes; c->leaf_nullable = leaf_nullable;
+  for (int32_t j = 0; j < n_nodes; ++j) { c->node_kind[j] = path[j].kind; c->node_null[j] = path[j].nullable; }
+  if (info_host) info_host->has_validity = leaf_nullable;   // (num_values = level entries: the bound of rows, items and values)
+  return DBHIP_OK;
+}
+
 }  // extern "C"
 
 // ---- the batch: one launch set for many chunks ------------------------------------------------------------------------------
@@ -1217,6 +1338,7 @@ int32_t decode_many(dbhip_pq_chunk* const* cs, int32_t n, const uint8_t* const* 
     if (out_status_host) out_status_host[i] = DBHIP_OK;
     DBHIP_REQUIRE(c && c->device_mode, "dbhip_pq_chunk_decode_device: the handle was not opened by dbhip_pq_chunk_open_device");
     DBHIP_REQUIRE(!c->list || list_pass, "dbhip_pq_chunk_decode_device: a List chunk is decoded by dbhip_pq_chunk_decode_device_list");
+    DBHIP_REQUIRE(!c->nested || list_pass, "dbhip_pq_chunk_decode_device: a nested leaf is decoded by dbhip_pq_chunk_decode_device_nested");
     // the arena of the previous decode, if the caller did not take it (dbhip_pq_chunk_take_arena)
     if (c->d_arena) { (void)dbhip_free(c->d_arena); c->d_arena = nullptr; c->arena_bytes = 0; }
     if (c->rows == 0) continue;
@@ -1284,7 +1406,7 @@ int32_t decode_many(dbhip_pq_chunk* const* cs, int32_t n, const uint8_t* const* 
   for (int i : live)
     if (cs[i]->codec == CODEC_ZSTD) n_z += cs[i]->pages.size();
   size_t jz = 0, jo = n_z;
-  bool any_list = false;
+  bool any_list = false, any_nested = false;
   unsigned max_slices = 1;
   for (size_t k = 0; k < nl; ++k) {
     const int i = live[k];
@@ -1327,6 +1449,12 @@ int32_t decode_many(dbhip_pq_chunk* const* cs, int32_t n, const uint8_t* const* 
       any_list = true;
       D.ldw = c->list_max_def > 1 ? 2u : 1u; D.lmax = (uint32_t)c->list_max_def; D.lnull = (uint32_t)c->list_nullable;
       D.isrep = c->d_isrep; D.iselem = c->d_iselem; D.lvalid = c->d_lvalid;
+      D.rw = 1; D.rmax = 1;
+    } else if (c->nested) {
+      any_list = true; any_nested = true;
+      D.ldw = bit_width_u32((uint32_t)c->nest_max_def); D.lmax = (uint32_t)c->nest_max_def;
+      D.rw = bit_width_u32((uint32_t)c->n_lists); D.rmax = (uint32_t)c->n_lists;
+      D.lrep = c->d_lrep; D.ldef = c->d_ldef;
     }
     if (c->dict_n > 0) dict_list[n_dict++] = (uint32_t)k;
     for (uint32_t d = 0; d < nd; ++d) {
@@ -1377,7 +1505,10 @@ int32_t decode_many(dbhip_pq_chunk* const* cs, int32_t n, const uint8_t* const* 
   if (n_z) hipLaunchKernelGGL(dv_inflate_zstd2_kernel, dim3((unsigned)n_z), dim3(128), ZW2_LDS, s, d_jobs, ZW_RING);
   if (n_jobs > n_z) hipLaunchKernelGGL(dv_inflate_lz_kernel, dim3((unsigned)(n_jobs - n_z)), dim3(64), LZ_RING, s, d_jobs + n_z, LZ_RING);
   if (n_dict) hipLaunchKernelGGL(dv_dict_kernel, dim3((unsigned)n_dict), dim3(256), 0, s, d_cds, (const uint32_t*)(blob + L.dict_list));
-  if (n_lv) hipLaunchKernelGGL(dv_levels_kernel, dim3((unsigned)n_lv), dim3(256), any_list ? LV_LDS : 0u, s, d_cds, (const uint2*)(blob + L.lv_map), any_list ? LV_LDS : 0u);
+  if (n_lv && any_nested)   // (a nested leaf is decoded alone: dbhip_pq_chunks_decode_device refuses its handle)
+    hipLaunchKernelGGL(dv_levels_kernel<true>, dim3((unsigned)n_lv), dim3(256), LV_LDS, s, d_cds, (const uint2*)(blob + L.lv_map), LV_LDS);
+  else if (n_lv)
+    hipLaunchKernelGGL(dv_levels_kernel<false>, dim3((unsigned)n_lv), dim3(256), any_list ? LV_LDS : 0u, s, d_cds, (const uint2*)(blob + L.lv_map), any_list ? LV_LDS : 0u);
   hipLaunchKernelGGL(dv_scan_kernel, dim3((unsigned)nl), dim3(256), 0, s, d_cds);
   if (k_dp) hipLaunchKernelGGL(dv_values_kernel, dim3((unsigned)k_dp, max_slices), dim3(256), 0, s, d_cds, (const uint2*)(blob + L.val_map));
   // DELTA_BYTE_ARRAY: size every page, read the sizes back (the one extra read-back, only for batches that hold such pages), give each chunk
@@ -1654,6 +1785,216 @@ int32_t decode_list(dbhip_pq_chunk* c, const uint8_t* chunk_dev, uint8_t* image_
   if (out_null_lists_host) *out_null_lists_host = (int64_t)hc[2];
   return DBHIP_OK;
 }
+
+// ---- nested leaves (any path of LIST / STRUCT nodes; include/dbhip.h has the rules) ----------------------------------------------
+// The levels kernel leaves every entry's (r, d) as bytes. Entry e opens a slot in space m iff r <= m && d >= Ê_m: per 32-entry word and
+// space, the slots are counted (pq_nest_count_kernel), scanned (one exclusive_scan_u32 per space), and the finish kernel gives each
+// entry its rank in every space from the word's offset + a ballot of its wave — no per-space bitmap is stored.
+struct NestK {
+  int32_t n_nodes, R, max_def, leaf_null;
+  int32_t kind[8], nul[8], V[8], space[8];
+  uint32_t E[5];          // Ê_m, m = 0..R (Ê_0 = 0)
+  uint64_t* off[8];       // LIST nodes: offsets
+  uint32_t* val[9];       // nullable nodes: validity; [8]: the leaf's
+};
+enum { NK_TOTAL = 0, NK_NULLS = 5, NK_BAD = 14, NK_WORDS = 16 };   // counts: [0..4] slots per space, [5..13] NULLs per node (13: the leaf)
+
+// Ê_r of a per-lane r (constant indices: the kernel arguments stay in scalar registers)
+__device__ __forceinline__ uint32_t nest_ehat(const NestK& K, uint32_t r) {
+  uint32_t e = 0;
+#pragma unroll
+  for (uint32_t m = 1; m < 5; ++m)
+    if (r == m) e = K.E[m];
+  return e;
+}
+
+// one entry per lane, whole waves: slots per word of every space (lane 0 writes the wave's two words) + the well-formedness rules
+__global__ __launch_bounds__(256) void pq_nest_count_kernel(const uint8_t* __restrict__ lrep, const uint8_t* __restrict__ ldef, int64_t entries, int64_t nwords,
+                                                            NestK K, uint32_t* __restrict__ scnt, unsigned long long* __restrict__ counts) {
+  const uint32_t lane = threadIdx.x & 63u;
+  for (int64_t base = (int64_t)blockIdx.x * 256 + (threadIdx.x & ~63u); base < entries; base += (int64_t)gridDim.x * 256) {
+    const int64_t e = base + lane;
+    const bool in = e < entries;
+    const uint32_t r = in ? lrep[e] : 0u, d = in ? ldef[e] : 0u;
+    const bool bad = in && ((e == 0 && r != 0) || (r > 0 && d < nest_ehat(K, r)));
+    if (__ballot(bad) != 0 && lane == 0) counts[NK_BAD] = 1;
+    const int64_t w0 = base >> 5;
+#pragma unroll
+    for (int m = 0; m < 5; ++m) {
+      if (m > K.R) break;
+      const uint64_t mk = __ballot(in && r <= (uint32_t)m && d >= K.E[m]);
+      if (lane == 0) {
+        scnt[m * nwords + w0] = (uint32_t)__popc((uint32_t)mk);
+        if (w0 + 1 < nwords) scnt[m * nwords + w0 + 1] = (uint32_t)__popc((uint32_t)(mk >> 32));
+      }
+    }
+  }
+}
+
+// per entry: for every node, a validity bit / an offset at its slot; the leaf value moves to its slot (BITS: a BOOLEAN leaf, the values
+// are a bitmap over the entries). ent_values of an entry without a value is zero (pq_spread), so a NULL slot gets zero bytes.
+template <typename V, bool BITS>
+__global__ __launch_bounds__(256) void pq_nest_finish_kernel(const uint8_t* __restrict__ lrep, const uint8_t* __restrict__ ldef, int64_t entries, int64_t nwords,
+                                                             NestK K, const uint32_t* __restrict__ scnt, const uint64_t* __restrict__ soff,
+                                                             const V* __restrict__ ent_values, V* __restrict__ out_values, unsigned long long* __restrict__ counts) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t lt = (1ull << lane) - 1ull;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    // the totals of every space; each LIST node's closing offset
+    uint64_t tot[5] = {0, 0, 0, 0, 0};
+#pragma unroll
+    for (int m = 0; m < 5; ++m)
+      if (m <= K.R) { tot[m] = soff[m * nwords + nwords - 1] + scnt[m * nwords + nwords - 1]; counts[NK_TOTAL + m] = tot[m]; }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (j >= K.n_nodes) break;
+      if (K.kind[j] != PQ_NODE_LIST) continue;
+      uint64_t own = 0, child = 0;
+#pragma unroll
+      for (int m = 0; m < 4; ++m)
+        if (K.space[j] == m) { own = tot[m]; child = tot[m + 1]; }
+      K.off[j][own] = child;
+    }
+  }
+  uint32_t nl[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int64_t base = (int64_t)blockIdx.x * 256 + (threadIdx.x & ~63u); base < entries; base += (int64_t)gridDim.x * 256) {
+    const int64_t e = base + lane;
+    const bool in = e < entries;
+    const uint32_t r = in ? lrep[e] : 0u, d = in ? ldef[e] : 0u;
+    const int64_t w0 = base >> 5;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (j >= K.n_nodes) break;
+      const int m = K.space[j];
+      const bool opens = in && r <= (uint32_t)m && d >= K.E[m];
+      const uint64_t mk = __ballot(opens);
+      if (mk == 0) continue;
+      const uint64_t rank = soff[m * nwords + w0] + (uint64_t)__popcll(mk & lt);
+      if (K.nul[j]) {
+        const bool v = opens && d >= (uint32_t)K.V[j];
+        list_put_bits(K.val[j], v, rank);
+        nl[j] += (uint32_t)__popcll(__ballot(opens && !v));
+      }
+      if (K.kind[j] == PQ_NODE_LIST) {
+        const uint64_t mc = __ballot(in && r <= (uint32_t)(m + 1) && d >= K.E[m + 1]);
+        if (opens) K.off[j][rank] = soff[(m + 1) * nwords + w0] + (uint64_t)__popcll(mc & lt);
+      }
+    }
+    // the leaf (space R)
+    const bool opens = in && r <= (uint32_t)K.R && d >= K.E[K.R];
+    const uint64_t mk = __ballot(opens);
+    if (mk == 0) continue;
+    const uint64_t rank = soff[K.R * nwords + w0] + (uint64_t)__popcll(mk & lt);
+    const bool valid = opens && d == (uint32_t)K.max_def;
+    if (BITS) {
+      const bool bit = valid && ((((const uint32_t*)ent_values)[e >> 5] >> (uint32_t)(e & 31)) & 1u);
+      list_put_bits((uint32_t*)out_values, bit, rank);
+    } else if (opens) {
+      out_values[rank] = ent_values[e];
+    }
+    if (K.leaf_null) {
+      list_put_bits(K.val[8], valid, rank);
+      nl[8] += (uint32_t)__popcll(__ballot(opens && !valid));
+    }
+  }
+  // NULL counts: one add per workgroup and node (adds on one word serialise in L2, see pq_list_finish_kernel)
+  __shared__ uint32_t wn[9][4];
+#pragma unroll
+  for (int j = 0; j < 9; ++j)
+    if (lane == 0) wn[j][threadIdx.x >> 6] = nl[j];
+  __syncthreads();
+  if (threadIdx.x < 9) {
+    const uint32_t t = wn[threadIdx.x][0] + wn[threadIdx.x][1] + wn[threadIdx.x][2] + wn[threadIdx.x][3];
+    if (t) atomicAdd(&counts[NK_NULLS + threadIdx.x], (unsigned long long)t);
+  }
+}
+
+int32_t decode_nested(dbhip_pq_chunk* c, const uint8_t* chunk_dev, uint8_t* image_dev, dbhip_pq_node_out* nodes, void* out_values_dev, int64_t* out_rows_host,
+                      void* stream) {
+  const char* who = "dbhip_pq_chunk_decode_device_nested";
+  DBHIP_REQUIRE(c && c->device_mode && c->nested, "dbhip_pq_chunk_decode_device_nested: the handle was not opened by dbhip_pq_chunk_open_device_nested");
+  DBHIP_REQUIRE(nodes && out_rows_host, "dbhip_pq_chunk_decode_device_nested: NULL argument");
+  const int nn = c->n_nodes;
+  for (int j = 0; j < nn; ++j) {
+    DBHIP_REQUIRE(c->node_kind[j] != PQ_NODE_LIST || nodes[j].offsets_dev, "dbhip_pq_chunk_decode_device_nested: a LIST node needs an offsets buffer");
+    DBHIP_REQUIRE(!c->node_null[j] || nodes[j].validity_dev, "dbhip_pq_chunk_decode_device_nested: a nullable node needs a validity buffer");
+  }
+  DBHIP_REQUIRE(!c->leaf_nullable || nodes[nn].validity_dev, "dbhip_pq_chunk_decode_device_nested: a nullable leaf needs a validity buffer");
+  for (int j = 0; j <= nn; ++j) { nodes[j].items = 0; nodes[j].nulls = 0; }
+  *out_rows_host = 0;
+  hipStream_t s = resolve_stream(stream);
+  const int64_t entries = c->rows;
+  if (entries == 0) {
+    for (int j = 0; j < nn; ++j)
+      if (c->node_kind[j] == PQ_NODE_LIST) DBHIP_CHECK(hipMemsetAsync(nodes[j].offsets_dev, 0, 8, s));
+    DBHIP_CHECK(hipStreamSynchronize(s));
+    return DBHIP_OK;
+  }
+  DBHIP_REQUIRE(out_values_dev, "dbhip_pq_chunk_decode_device_nested: NULL values buffer");
+  const int esize = out_elem_size(c->out_type);
+  const bool is_bool = c->out_type == DBHIP_T_BOOL;
+  const int R = c->n_lists;
+  const int64_t nwords = ceil_div(entries, 32), wbytes = ceil_div(entries, 64) * 8;
+  if (!c->d_lrep) DBHIP_TRY(dbhip_alloc((size_t)entries + 16, (void**)&c->d_lrep));
+  if (!c->d_ldef) DBHIP_TRY(dbhip_alloc((size_t)entries + 16, (void**)&c->d_ldef));
+  if (!c->d_ent_valid) DBHIP_TRY(dbhip_alloc((size_t)wbytes, (void**)&c->d_ent_valid));
+  if (!c->d_ent_values) DBHIP_TRY(dbhip_alloc(is_bool ? (size_t)wbytes : (size_t)entries * (size_t)esize, &c->d_ent_values));
+  if (!c->d_scnt) DBHIP_TRY(dbhip_alloc((size_t)(R + 1) * (size_t)nwords * 4, (void**)&c->d_scnt));
+  if (!c->d_soff) DBHIP_TRY(dbhip_alloc((size_t)(R + 1) * (size_t)nwords * 8, (void**)&c->d_soff));
+  if (!c->d_lblk) DBHIP_TRY(dbhip_alloc((size_t)(ceil_div(nwords, SCAN_TILE) + 2) * 8, (void**)&c->d_lblk));
+  if (!c->d_lcounts) DBHIP_TRY(dbhip_alloc(NK_WORDS * 8, (void**)&c->d_lcounts));
+  // levels the pages do not carry read as 0: no LIST above the leaf (no repetition stream), no levels at all (max_def_level 0)
+  if (R == 0) DBHIP_CHECK(hipMemsetAsync(c->d_lrep, 0, (size_t)entries, s));
+  if (c->nest_max_def == 0) DBHIP_CHECK(hipMemsetAsync(c->d_ldef, 0, (size_t)entries, s));
+  DBHIP_CHECK(hipMemsetAsync(c->d_lcounts, 0, NK_WORDS * 8, s));
+  void* ent_values = c->d_ent_values;
+  uint8_t* ent_valid = (uint8_t*)c->d_ent_valid;
+  int64_t ent_nulls = 0;
+  int32_t rc = decode_many(&c, 1, &chunk_dev, &image_dev, &ent_values, &ent_valid, &ent_nulls, nullptr, stream, true);
+  if (rc) return rc;
+  NestK K{};
+  K.n_nodes = nn; K.R = R; K.max_def = c->nest_max_def; K.leaf_null = c->leaf_nullable;
+  uint32_t before = 0;
+  int lists = 0;
+  for (int j = 0; j < nn; ++j) {
+    K.kind[j] = c->node_kind[j]; K.nul[j] = c->node_null[j];
+    K.space[j] = lists;
+    K.V[j] = (int32_t)(before + (uint32_t)c->node_null[j]);
+    before += (uint32_t)c->node_null[j];
+    if (c->node_kind[j] == PQ_NODE_LIST) { K.E[++lists] = ++before; K.off[j] = nodes[j].offsets_dev; }
+    if (c->node_null[j]) K.val[j] = (uint32_t*)nodes[j].validity_dev;
+    if (nodes[j].validity_dev) DBHIP_CHECK(hipMemsetAsync(nodes[j].validity_dev, c->node_null[j] ? 0 : 0xFF, (size_t)wbytes, s));
+  }
+  if (c->leaf_nullable) K.val[8] = (uint32_t*)nodes[nn].validity_dev;
+  if (nodes[nn].validity_dev) DBHIP_CHECK(hipMemsetAsync(nodes[nn].validity_dev, c->leaf_nullable ? 0 : 0xFF, (size_t)wbytes, s));
+  if (is_bool) DBHIP_CHECK(hipMemsetAsync(out_values_dev, 0, (size_t)wbytes, s));
+  unsigned long long* counts = (unsigned long long*)c->d_lcounts;
+  const int grid = grid_for(entries, 256) < 2048 ? grid_for(entries, 256) : 2048;
+  hipLaunchKernelGGL(pq_nest_count_kernel, dim3(grid), dim3(256), 0, s, c->d_lrep, c->d_ldef, entries, nwords, K, c->d_scnt, counts);
+  for (int m = 0; m <= R; ++m) DBHIP_TRY(dbscan::exclusive_scan_u32(c->d_scnt + (size_t)m * nwords, nwords, c->d_lblk, c->d_soff + (size_t)m * nwords, s));
+#define NEST_FINISH(V_, B_) hipLaunchKernelGGL((pq_nest_finish_kernel<V_, B_>), dim3(grid), dim3(256), 0, s, c->d_lrep, c->d_ldef, entries, nwords, K, \
+                                               c->d_scnt, c->d_soff, (const V_*)c->d_ent_values, (V_*)out_values_dev, counts)
+  if (is_bool) NEST_FINISH(uint32_t, true);
+  else if (esize == 1) NEST_FINISH(uint8_t, false);
+  else if (esize == 2) NEST_FINISH(uint16_t, false);
+  else if (esize == 4) NEST_FINISH(uint32_t, false);
+  else if (esize == 8) NEST_FINISH(uint64_t, false);
+  else NEST_FINISH(uint4, false);
+#undef NEST_FINISH
+  DBHIP_LAUNCH_CHECK();
+  unsigned long long hc[NK_WORDS] = {};
+  DBHIP_CHECK(hipMemcpyAsync(hc, counts, sizeof(hc), hipMemcpyDeviceToHost, s));
+  DBHIP_CHECK(hipStreamSynchronize(s));
+  if (hc[NK_BAD]) {
+    set_error("%s: malformed column chunk (the first level entry continues a row, or a repetition level has no element of its list)", who);
+    return DBHIP_ERR_INVALID;
+  }
+  *out_rows_host = (int64_t)hc[NK_TOTAL];
+  for (int j = 0; j < nn; ++j) { nodes[j].items = (int64_t)hc[NK_TOTAL + K.space[j]]; nodes[j].nulls = (int64_t)hc[NK_NULLS + j]; }
+  nodes[nn].items = (int64_t)hc[NK_TOTAL + R];
+  nodes[nn].nulls = (int64_t)hc[NK_NULLS + 8];
+  return DBHIP_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1663,6 +2004,11 @@ int32_t dbhip_pq_chunk_decode_device_list(dbhip_pq_chunk* c, const uint8_t* chun
                                           int64_t* out_rows_host, int64_t* out_elems_host, int64_t* out_null_lists_host, void* stream) {
   return decode_list(c, chunk_dev, image_dev, out_offsets_dev, out_list_validity_dev, out_values_dev, out_elem_validity_dev, out_rows_host, out_elems_host,
                      out_null_lists_host, stream);
+}
+
+int32_t dbhip_pq_chunk_decode_device_nested(dbhip_pq_chunk* c, const uint8_t* chunk_dev, uint8_t* image_dev, dbhip_pq_node_out* nodes_host,
+                                            void* out_values_dev, int64_t* out_rows_host, void* stream) {
+  return decode_nested(c, chunk_dev, image_dev, nodes_host, out_values_dev, out_rows_host, stream);
 }
 
 int32_t dbhip_pq_chunk_take_arena(dbhip_pq_chunk* c, void** out_dev_ptr_host, int64_t* out_bytes_host) {

@@ -228,6 +228,13 @@ struct dbhip_pq_chunk {
   void* d_ent_values = nullptr;
   uint32_t* d_rcnt = nullptr; uint32_t* d_ecnt = nullptr; uint64_t* d_roff = nullptr; uint64_t* d_eoff = nullptr; uint64_t* d_lblk = nullptr;
   uint64_t* d_lcounts = nullptr;
+  // nested leaves (dbhip_pq_chunk_open_device_nested): `rows` counts LEVEL ENTRIES as for a List; the levels kernel writes every entry's
+  // (r, d) as bytes (d_lrep / d_ldef) and the leaf's carries-a-value bitmap (d_ent_valid), the nested pass builds the slots of every space
+  bool nested = false;
+  int32_t n_nodes = 0, n_lists = 0, nest_max_def = 0, leaf_nullable = 0;
+  int32_t node_kind[8] = {}, node_null[8] = {};
+  uint8_t* d_lrep = nullptr; uint8_t* d_ldef = nullptr;
+  uint32_t* d_scnt = nullptr; uint64_t* d_soff = nullptr;   // per space: slots per 32-entry word, and their exclusive scan
   // DELTA_BYTE_ARRAY pages: their values, materialised by the last decode into one arena (buffer 1 of a String column); owned by the handle
   // until dbhip_pq_chunk_take_arena hands it over, freed by the next decode or close otherwise
   void* d_arena = nullptr;

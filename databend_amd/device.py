@@ -1909,19 +1909,31 @@ class ParquetChunk:
     `chunk` = the raw bytes of the column chunk (dictionary page first), as the block reader fetched them."""
 
     def __init__(self, chunk, physical_type, out_type, type_length=0, max_def_level=0, max_rep_level=0, codec=0,
-                 precision=0, scale=0, device=False, list_of=None):
+                 precision=0, scale=0, device=False, list_of=None, nested=None, leaf_nullable=False):
         """device=True: dbhip_pq_chunk_open_device / _decode_device — the host reads the page headers only; decompression (ZSTD / SNAPPY /
         LZ4_RAW), run headers, length prefixes and DELTA blocks are walked on the GPU from the chunk as stored.
-        list_of=(list_nullable, element_nullable): a List<primitive> leaf (dbhip_pq_chunk_open_device_list; decode with decode_list())."""
+        list_of=(list_nullable, element_nullable): a List<primitive> leaf (dbhip_pq_chunk_open_device_list; decode with decode_list()).
+        nested=[("list" | "struct", nullable), ...]: the path of a nested leaf, outermost node first, with leaf_nullable
+        (dbhip_pq_chunk_open_device_nested; decode with decode_nested())."""
         _ensure()
         self.host = np.frombuffer(chunk, dtype=np.uint8)   # zero-copy view; the bytes object stays referenced by the array
         self.out_type, self.precision, self.scale = out_type, precision, scale
-        self.device = bool(device) or list_of is not None
+        self.device = bool(device) or list_of is not None or nested is not None
         self.list_of = list_of
+        self.nested = None
+        if nested is not None:
+            kinds = {"list": L.PQ_LIST, "struct": L.PQ_STRUCT}
+            self.nested = [(kinds.get(k, k) if isinstance(k, str) else int(k), int(n)) for k, n in nested]
+        self.leaf_nullable = int(leaf_nullable)
         self.h = C.c_void_p()
         self.info = L.PqInfo()
         hp = self.host.ctypes.data_as(C.c_void_p) if len(self.host) else C.c_void_p(0)
-        if list_of is not None:
+        if self.nested is not None:
+            path = (L.PqNode * max(len(self.nested), 1))(*[L.PqNode(k, n) for k, n in self.nested])
+            check(lib().dbhip_pq_chunk_open_device_nested(hp if len(self.host) else self.host.ctypes.data_as(C.c_void_p), C.c_int64(len(self.host)), C.c_int32(codec), C.c_int32(physical_type), C.c_int32(type_length),
+                                                          path, C.c_int32(len(self.nested)), C.c_int32(self.leaf_nullable), C.c_int32(out_type),
+                                                          C.byref(self.h), C.byref(self.info)))
+        elif list_of is not None:
             check(lib().dbhip_pq_chunk_open_device_list(hp, C.c_int64(len(self.host)), C.c_int32(codec), C.c_int32(physical_type), C.c_int32(type_length),
                                                         C.c_int32(1 if list_of[0] else 0), C.c_int32(1 if list_of[1] else 0), C.c_int32(out_type),
                                                         C.byref(self.h), C.byref(self.info)))
@@ -2015,6 +2027,43 @@ class ParquetChunk:
         col.n_buffers = len(keep) if bufs is not None else 0
         lv = unpack_bits(lval.to_numpy(np.uint8, (rows.value + 7) // 8), rows.value) if lval is not None else None
         return offs.to_numpy(np.uint64, rows.value + 1), lv, col
+
+    def decode_nested(self, stream=None):
+        """dbhip_pq_chunk_decode_device_nested -> ([(offsets numpy u64 [items + 1] or None, validity numpy bool [items] or None, items,
+        nulls) per path node], leaf Column). A LIST node has offsets, a nullable node validity; the leaf's own validity is the Column's."""
+        i = self.info
+        nodes = self.nested
+        chunk_dev = self.upload()
+        if i.image_bytes and self.image_dev is None:
+            self.image_dev = DeviceBuffer(i.image_bytes)
+        outs = (L.PqNodeOut * (len(nodes) + 1))()
+        bufs_keep = []
+        for j, (kind, nullable) in enumerate(nodes):
+            offs = DeviceBuffer((i.num_values + 1) * 8 + 16) if kind == L.PQ_LIST else None
+            val = DeviceBuffer(i.validity_bytes + 8) if nullable else None
+            outs[j].offsets_dev = offs.ptr if offs is not None else None
+            outs[j].validity_dev = val.ptr if val is not None else None
+            bufs_keep.append((offs, val))
+        leaf_val = DeviceBuffer(i.validity_bytes + 8) if self.leaf_nullable else None
+        outs[len(nodes)].validity_dev = leaf_val.ptr if leaf_val is not None else None
+        out = DeviceBuffer(i.out_bytes + 16)
+        rows = C.c_int64()
+        check(lib().dbhip_pq_chunk_decode_device_nested(self.h, C.c_void_p(chunk_dev.ptr), C.c_void_p(self.image_dev.ptr) if self.image_dev else None,
+                                                        outs, C.c_void_p(out.ptr), C.byref(rows), stream))
+        self.rows = rows.value
+        res = []
+        for j, (offs, val) in enumerate(bufs_keep):
+            n = outs[j].items
+            o = offs.to_numpy(np.uint64, n + 1) if offs is not None else None
+            v = unpack_bits(val.to_numpy(np.uint8, (n + 7) // 8), n) if val is not None else None
+            res.append((o, v, n, outs[j].nulls))
+        leaf = outs[len(nodes)]
+        buf0 = self.image_dev if self.image_dev is not None else chunk_dev
+        bufs, keep = self._string_buffers(buf0) if self.out_type == L.T_STRING else (None, (buf0,))
+        col = Column(self.out_type, leaf.items, out, leaf_val, self.precision, self.scale, buffers=bufs, keep=keep)
+        col.n_buffers = len(keep) if bufs is not None else 0
+        self.leaf_nulls = leaf.nulls
+        return res, col
 
     @staticmethod
     def decode_many(chunks, stream=None, statuses=None):

@@ -2129,4 +2129,70 @@ inline std::optional<ListColumn> list_chunk_to_column(const uint8_t* bytes, size
   return L;
 }
 
+// A nested leaf (dbhip_pq_chunk_open_device_nested): every node of its path, outermost first — a LIST node's offsets (items + 1), a
+// nullable node's validity (one byte per slot) — and the leaf column. Databend assembles Array / Map / Tuple columns from them
+// (INTEGRATION.md §13d). std::nullopt where the device path declines the chunk (DBHIP_ERR_UNSUPPORTED: keep arrow-rs).
+constexpr int32_t PQ_NODE_LIST = 1, PQ_NODE_STRUCT = 2;   // dbhip_pq_node.kind
+struct NestedNode {
+  int32_t kind = PQ_NODE_LIST;
+  bool nullable = false;
+  int64_t items = 0, nulls = 0;
+  std::vector<uint64_t> offsets;   // LIST nodes
+  std::vector<uint8_t> valid;      // nullable nodes
+};
+struct NestedColumn {
+  int64_t rows = 0;
+  std::vector<NestedNode> nodes;
+  Column leaf;
+};
+inline std::optional<NestedColumn> nested_chunk_to_column(const uint8_t* bytes, size_t len, const ParquetLeaf& leaf, const std::vector<dbhip_pq_node>& path,
+                                                          bool leaf_nullable, DataType leaf_type) {
+  dbhip_pq_chunk* h = nullptr;
+  dbhip_pq_info info;
+  const int32_t rc = dbhip_pq_chunk_open_device_nested(bytes, (int64_t)len, leaf.codec, leaf.physical_type, leaf.type_length, path.data(),
+                                                       (int32_t)path.size(), leaf_nullable ? 1 : 0, leaf_type.id, &h, &info);
+  if (rc == DBHIP_ERR_UNSUPPORTED) return std::nullopt;
+  check(rc);
+  struct Closer { dbhip_pq_chunk* h; ~Closer() { dbhip_pq_chunk_close(h); } } closer{h};
+  Buf chunk = make_buf(len + 32), image = info.image_bytes ? make_buf((size_t)info.image_bytes) : nullptr;
+  chunk->upload(bytes, len);
+  std::vector<Buf> offs(path.size()), vals(path.size());
+  std::vector<dbhip_pq_node_out> outs(path.size() + 1);
+  for (size_t j = 0; j < path.size(); ++j) {
+    if (path[j].kind == PQ_NODE_LIST) offs[j] = make_buf((size_t)(info.num_values + 1) * 8 + 16);
+    if (path[j].nullable) vals[j] = make_buf((size_t)info.validity_bytes + 8);
+    outs[j] = dbhip_pq_node_out{offs[j] ? (uint64_t*)offs[j]->ptr() : nullptr, vals[j] ? (uint8_t*)vals[j]->ptr() : nullptr, 0, 0};
+  }
+  NestedColumn N;
+  Column& c = N.leaf;
+  c.type = leaf_type;
+  c.type.nullable = leaf_nullable;
+  c.data = make_buf((size_t)info.out_bytes + 16);
+  if (leaf_nullable) c.validity = make_buf((size_t)info.validity_bytes + 8);
+  outs[path.size()] = dbhip_pq_node_out{nullptr, c.validity ? (uint8_t*)c.validity->ptr() : nullptr, 0, 0};
+  check(dbhip_pq_chunk_decode_device_nested(h, (const uint8_t*)chunk->ptr(), image ? (uint8_t*)image->ptr() : nullptr, outs.data(), c.data->ptr(),
+                                            &N.rows, nullptr));
+  c.len = outs[path.size()].items;
+  N.nodes.resize(path.size());
+  for (size_t j = 0; j < path.size(); ++j) {
+    NestedNode& n = N.nodes[j];
+    n.kind = path[j].kind;
+    n.nullable = path[j].nullable != 0;
+    n.items = outs[j].items;
+    n.nulls = outs[j].nulls;
+    if (offs[j]) {
+      n.offsets.resize((size_t)n.items + 1);
+      offs[j]->download(n.offsets.data(), n.offsets.size() * 8);
+    }
+    if (vals[j]) {
+      std::vector<uint8_t> bits((size_t)(n.items + 7) / 8);
+      if (!bits.empty()) vals[j]->download(bits.data(), bits.size());
+      n.valid.resize((size_t)n.items);
+      for (int64_t r = 0; r < n.items; ++r) n.valid[(size_t)r] = (bits[(size_t)r >> 3] >> (r & 7)) & 1;
+    }
+  }
+  if (leaf_type.id == DBHIP_T_STRING) set_string_buffers(c, image ? image : chunk, h);
+  return N;
+}
+
 }  // namespace dbhip_host

@@ -973,6 +973,28 @@ static void test_parquet_device_mode() {
     auto ok = L->elements.validity_to_host();
     CHECK(L->elements.len == 3 && v[0] == 5 && v[1] == 0 && v[2] == 6 && ok[0] && !ok[1] && ok[2]);
   }
+  // List<List<Int64>>, every level nullable (max_def 5, max_rep 2): rows [[1, NULL], NULL, []], NULL, [[], [2]] -> entries (rep, def):
+  // (0,5) (2,4) (1,2) (1,3) (0,0) (0,3) (1,5)
+  std::vector<uint8_t> ll = {
+      0x15, 0x00, 0x15, 0x68, 0x15, 0x68, 0x2C, 0x15, 0x0E, 0x15, 0x00, 0x15, 0x06, 0x15, 0x06, 0x00, 0x00,   // DATA_PAGE, 52 bytes, 7 entries
+      0x0E, 0x00, 0x00, 0x00, 0x02, 0, 0x02, 2, 0x02, 1, 0x02, 1, 0x02, 0, 0x02, 0, 0x02, 1,     // repetition levels: one RLE run per entry
+      0x0E, 0x00, 0x00, 0x00, 0x02, 5, 0x02, 4, 0x02, 2, 0x02, 3, 0x02, 0, 0x02, 3, 0x02, 5,     // definition levels
+  };
+  const int64_t ll_vals[2] = {1, 2};
+  ll.insert(ll.end(), (const uint8_t*)ll_vals, (const uint8_t*)ll_vals + 16);
+  auto N = nested_chunk_to_column(ll.data(), ll.size(), ParquetLeaf{2, 0, 5, 2, 0}, {dbhip_pq_node{PQ_NODE_LIST, 1}, dbhip_pq_node{PQ_NODE_LIST, 1}}, true,
+                                  DataType::of(DBHIP_T_I64));
+  CHECK(N.has_value());
+  if (N) {
+    CHECK(N->rows == 3 && N->nodes.size() == 2);
+    CHECK(N->nodes[0].items == 3 && N->nodes[0].nulls == 1 && N->nodes[0].offsets == (std::vector<uint64_t>{0, 3, 3, 5}));
+    CHECK(N->nodes[0].valid == (std::vector<uint8_t>{1, 0, 1}));
+    CHECK(N->nodes[1].items == 5 && N->nodes[1].nulls == 1 && N->nodes[1].offsets == (std::vector<uint64_t>{0, 2, 2, 2, 2, 3}));
+    CHECK(N->nodes[1].valid == (std::vector<uint8_t>{1, 0, 1, 1, 1}));
+    auto v = N->leaf.to_vector<int64_t>();
+    auto ok = N->leaf.validity_to_host();
+    CHECK(N->leaf.len == 3 && v[0] == 1 && v[1] == 0 && v[2] == 2 && ok[0] && !ok[1] && ok[2]);
+  }
 }
 
 int main() {

@@ -1006,13 +1006,52 @@ int32_t dbhip_pq_chunks_decode_device(dbhip_pq_chunk* const* chunks, int32_t n_c
  * out_list_validity (list_nullable; a NULL list is an empty run), out_values the elements back to back in the output type (a NULL
  * element decodes to 0), out_elem_validity (element_nullable); the row / element / NULL-list counts come back to the host. String
  * elements are views into chunk_dev / the image like a flat String chunk's. Deeper nesting (List<List<..>>, Map, Tuple members):
- * DBHIP_ERR_UNSUPPORTED from the flat open — the binding keeps arrow-rs. */
+ * DBHIP_ERR_UNSUPPORTED from the flat open; dbhip_pq_chunk_open_device_nested below decodes it. */
 int32_t dbhip_pq_chunk_open_device_list(const uint8_t* chunk_host, int64_t chunk_len, int32_t codec, int32_t physical_type, int32_t type_length,
                                         int32_t list_nullable, int32_t element_nullable, int32_t out_type, dbhip_pq_chunk** out_host,
                                         dbhip_pq_info* info_host);
 int32_t dbhip_pq_chunk_decode_device_list(dbhip_pq_chunk* c, const uint8_t* chunk_dev, uint8_t* image_dev, uint64_t* out_offsets_dev,
                                           uint8_t* out_list_validity_dev, void* out_values_dev, uint8_t* out_elem_validity_dev,
                                           int64_t* out_rows_host, int64_t* out_elems_host, int64_t* out_null_lists_host, void* stream);
+/* Nested leaves (any path of LIST and STRUCT nodes: List<List<..>>, Map values, Tuple members, nullable Tuples). A leaf is described by
+ * its PATH, the nodes from the column root down to the leaf's parent, outermost first, each {kind, nullable} (kind 1 = LIST, 2 =
+ * STRUCT), plus leaf_nullable.
+ * Databend types map onto it as: Array(T) = a LIST node; Tuple(..) = a STRUCT node for each member leaf; Map(K, V) = a LIST node, then
+ * a required STRUCT node (the key / value pair), then K's or V's own path; Nullable(X) sets the nullable flag of X's node or of the
+ * leaf. So max_rep_level = number of LIST nodes (R), max_def_level = sum of the nullable flags + R + leaf_nullable.
+ *   Definition thresholds: walk the path keeping `before` (levels used so far, from 0): node j is non-NULL when d >= V_j =
+ *   before + nullable_j, then before += nullable_j; a LIST node's element exists when d >= E_j = before + 1, then before += 1. The leaf
+ *   is valid when d == max_def_level.
+ *   Index spaces: space 0 holds the rows, space m (1..R) the elements of the m-th LIST node. A node's slots live in the space of its
+ *   nearest enclosing LIST (space 0 if none); STRUCT nodes open no space; the leaf's slots live in space R. With Ê_0 = 0 and Ê_m the
+ *   E of the m-th LIST node, level entry e with levels (r, d) opens a slot in space m iff r <= m && d >= Ê_m. At each slot it opens,
+ *   every node living in that space gets one validity bit (d >= V_j), every LIST node living there one offset (the space-(m+1) slots
+ *   opened by the entries before e); after the last entry each LIST node gets one more offset, the total. Leaf slot k takes the k-th
+ *   value when the leaf is valid and ZERO BYTES otherwise (a zero 16-byte view for a string, a 0 bit for BOOLEAN).
+ *   Well-formed levels (else DBHIP_ERR_INVALID at decode): r(0) == 0; r <= R and d <= max_def_level; r > 0 implies d >= Ê_r.
+ * Limits: 1..8 nodes, at most 4 of them LIST (DBHIP_ERR_UNSUPPORTED beyond); a kind other than LIST / STRUCT, a flag other than 0 / 1
+ * or a NULL path is DBHIP_ERR_INVALID. open_device_nested reads page headers only, with open_device's encodings and type pairs (v1 pages
+ * need RLE levels); info.num_values is the number of LEVEL ENTRIES and bounds every output: size each LIST node's offsets for
+ * (num_values + 1) u64, each validity for info.validity_bytes, the leaf values for info.out_bytes. decode_device_nested takes n_nodes + 1
+ * dbhip_pq_node_out entries (the last one the leaf: offsets_dev unused, validity_dev when leaf_nullable), fills items / nulls of each
+ * and the row count. String leaves are views into chunk_dev / the image (DELTA_BYTE_ARRAY: the arena of dbhip_pq_chunk_take_arena),
+ * BOOLEAN leaves a bitmap. dbhip_pq_chunks_decode_device refuses a nested handle; the host-mode dbhip_pq_chunk_open keeps refusing
+ * nested leaves. */
+typedef struct dbhip_pq_node {
+  int32_t kind;       /* 1 = LIST, 2 = STRUCT */
+  int32_t nullable;   /* 0 / 1 */
+} dbhip_pq_node;
+typedef struct dbhip_pq_node_out {
+  uint64_t* offsets_dev;   /* LIST nodes: (info.num_values + 1) u64, else NULL                        (in)  */
+  uint8_t* validity_dev;   /* nullable nodes / a nullable leaf: info.validity_bytes, else NULL         (in)  */
+  int64_t items;           /* slots of this node (the leaf's: its value count)                        (out) */
+  int64_t nulls;           /* NULL slots                                                              (out) */
+} dbhip_pq_node_out;
+int32_t dbhip_pq_chunk_open_device_nested(const uint8_t* chunk_host, int64_t chunk_len, int32_t codec, int32_t physical_type,
+                                          int32_t type_length, const dbhip_pq_node* path, int32_t n_nodes, int32_t leaf_nullable,
+                                          int32_t out_type, dbhip_pq_chunk** out_host, dbhip_pq_info* info_host);
+int32_t dbhip_pq_chunk_decode_device_nested(dbhip_pq_chunk* c, const uint8_t* chunk_dev, uint8_t* image_dev,
+                                            dbhip_pq_node_out* nodes_host, void* out_values_dev, int64_t* out_rows_host, void* stream);
 /* DELTA_BYTE_ARRAY pages (device mode): their values exist nowhere back to back, so decode_device / decode_device_list (and
  * chunks_decode_device) materialise them into one ARENA per chunk, a device allocation of the library; the long views of such values
  * point into it as buffer 1 of the column (buffer 0 stays the chunk / the image). take_arena hands the caller the arena of the last
