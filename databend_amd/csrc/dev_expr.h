@@ -17,6 +17,12 @@
 #include "dev_decimal.h"
 #include "dev_load.h"
 
+// Every node of a program rounds once, like the reference's evaluator, which materialises a column per call node: `x * 0.5 + y` is a
+// multiply and an add, never a fused multiply-add. The interpreting kernels cannot fuse (one instruction per step); the run-time
+// specialised kernel (DBHIP_JIT: this text with the program as a constant) would — hipcc contracts by default — and then differs
+// from both on operands whose product is inexact (tests/test_gpu_float_edges.py::test_fused_float_map_specialised).
+#pragma clang fp contract(off)
+
 constexpr int EX_MAX_INS = 24;
 constexpr int EX_MAX_REGS = 16;    // user registers
 constexpr int EX_MAX_INPUTS = 8;

@@ -275,12 +275,18 @@ __global__ __launch_bounds__(256) void sum_f64_partial_kernel(SumParams p, doubl
        q += (int64_t)gridDim.x * blockDim.x) {
     uint64_t v[4];
     load4_wide(p.data, p.type, false, q << 2, p.n, v);
+    // the rows that count, as a mask, before any value is touched. (Written as `acc += ok ? value : 0.0` per row, hipcc 7 emitted
+    // an EMPTY predicated block for the first row of every quad of a column with a validity Bitmap: that row never reached the sum —
+    // tests/test_gpu_float_edges.py::test_column_sum_of_floats.)
+    uint32_t okm = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      int64_t row = (q << 2) + k;
-      bool ok = row < p.n && (!p.validity || bit_get(p.validity, p.voff + row));
-      acc += ok ? __longlong_as_double((long long)v[k]) : 0.0;
+      const int64_t row = (q << 2) + k;
+      okm |= (uint32_t)(row < p.n && (!p.validity || bit_get(p.validity, p.voff + row))) << k;
     }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if ((okm >> k) & 1u) acc += __longlong_as_double((long long)v[k]);
   }
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
