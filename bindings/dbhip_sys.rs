@@ -66,6 +66,22 @@ pub const DBHIP_AGG_COUNT: i32 = 0;   // dbhip_agg_kind
 pub const DBHIP_AGG_SUM: i32 = 1;   // dbhip_agg_kind
 pub const DBHIP_AGG_MIN: i32 = 2;   // dbhip_agg_kind
 pub const DBHIP_AGG_MAX: i32 = 3;   // dbhip_agg_kind
+pub const DBHIP_WIN_ROWS: i32 = 0;   // dbhip_window_units
+pub const DBHIP_WIN_RANGE: i32 = 1;   // dbhip_window_units
+pub const DBHIP_WIN_UNBOUNDED_PRECEDING: i32 = 0;   // dbhip_window_bound
+pub const DBHIP_WIN_PRECEDING: i32 = 1;   // dbhip_window_bound
+pub const DBHIP_WIN_CURRENT_ROW: i32 = 2;   // dbhip_window_bound
+pub const DBHIP_WIN_FOLLOWING: i32 = 3;   // dbhip_window_bound
+pub const DBHIP_WIN_UNBOUNDED_FOLLOWING: i32 = 4;   // dbhip_window_bound
+pub const DBHIP_WIN_ROW_NUMBER: i32 = 0;   // dbhip_window_rank_kind
+pub const DBHIP_WIN_RANK: i32 = 1;   // dbhip_window_rank_kind
+pub const DBHIP_WIN_DENSE_RANK: i32 = 2;   // dbhip_window_rank_kind
+pub const DBHIP_WIN_PERCENT_RANK: i32 = 3;   // dbhip_window_rank_kind
+pub const DBHIP_WIN_CUME_DIST: i32 = 4;   // dbhip_window_rank_kind
+pub const DBHIP_WIN_NTILE: i32 = 5;   // dbhip_window_rank_kind
+pub const DBHIP_WIN_FIRST_VALUE: i32 = 0;   // dbhip_window_value_kind
+pub const DBHIP_WIN_LAST_VALUE: i32 = 1;   // dbhip_window_value_kind
+pub const DBHIP_WIN_NTH_VALUE: i32 = 2;   // dbhip_window_value_kind
 pub const DBHIP_VEC_COSINE: i32 = 0;   // dbhip_vec_metric
 pub const DBHIP_VEC_L2: i32 = 1;   // dbhip_vec_metric
 pub const DBHIP_VEC_DOT: i32 = 2;   // dbhip_vec_metric
@@ -139,6 +155,27 @@ pub struct dbhip_agg_program {
     pub n_inputs: i32,
     pub filter_reg: i32,
     pub arg_regs: *const i32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct dbhip_window_rows {
+    pub n: i64,
+    pub part_start: *mut u32,
+    pub part_end: *mut u32,
+    pub peer_start: *mut u32,
+    pub peer_end: *mut u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct dbhip_window_frame {
+    pub units: i32,
+    pub start_kind: i32,
+    pub end_kind: i32,
+    pub _pad: i32,
+    pub start_offset: i64,
+    pub end_offset: i64,
 }
 
 #[repr(C)]
@@ -275,6 +312,11 @@ extern "C" {
     pub fn dbhip_sort_perm(keys: *const dbhip_col, desc_host: *const u8, nulls_first_host: *const u8, nkeys: i32, n: i64, limit: i64, out_perm: *mut u32, stream: *mut c_void) -> i32;
     pub fn dbhip_merge_sorted_perm(keys: *const dbhip_col, desc_host: *const u8, nulls_first_host: *const u8, nkeys: i32, run_offsets_host: *const i64, nruns: i32, limit: i64, out_perm: *mut u32, stream: *mut c_void) -> i32;
     pub fn dbhip_sort_bound_partition(keys: *const dbhip_col, bounds: *const dbhip_col, desc_host: *const u8, nulls_first_host: *const u8, nkeys: i32, n: i64, nbounds: i64, out_part: *mut u32, out_counts: *mut u64, stream: *mut c_void) -> i32;
+    pub fn dbhip_window_bounds(partition_keys: *const dbhip_col, n_partition: i32, order_keys: *const dbhip_col, n_order: i32, n: i64, rows: *mut dbhip_window_rows, stream: *mut c_void) -> i32;
+    pub fn dbhip_window_rank(rows: *const dbhip_window_rows, kind: i32, buckets: u64, out: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn dbhip_window_shift(rows: *const dbhip_window_rows, arg: *const dbhip_col, offset: i64, dflt: *const dbhip_col, out: *mut c_void, out_validity: *mut u8, stream: *mut c_void) -> i32;
+    pub fn dbhip_window_value(rows: *const dbhip_window_rows, kind: i32, nth: i64, arg: *const dbhip_col, frame: *const dbhip_window_frame, out: *mut c_void, out_validity: *mut u8, stream: *mut c_void) -> i32;
+    pub fn dbhip_window_aggregate(rows: *const dbhip_window_rows, agg: *const dbhip_agg_desc, arg: *const dbhip_col, frame: *const dbhip_window_frame, out: *mut c_void, out_validity: *mut u8, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_distance_rows(metric: i32, elem_type: i32, lhs: *const c_void, lhs_is_scalar: i32, rhs: *const c_void, rhs_is_scalar: i32, n: i64, dim: i32, out: *mut c_void, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_distance(metric: i32, base: *const f32, n: i64, dim: i32, queries: *const f32, nq: i32, out: *mut f32, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_topk(metric: i32, base: *const f32, n: i64, dim: i32, queries: *const f32, nq: i32, k: i32, out_idx: *mut u32, out_dist: *mut f32, stream: *mut c_void) -> i32;

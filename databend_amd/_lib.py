@@ -80,6 +80,23 @@ class AggDesc(C.Structure):
                 ("arg_scale", C.c_uint8), ("arg_nullable", C.c_uint8), ("_pad", C.c_uint8)]
 
 
+class WindowRows(C.Structure):
+    """dbhip_window_rows"""
+    _fields_ = [("n", C.c_int64), ("part_start", C.c_void_p), ("part_end", C.c_void_p), ("peer_start", C.c_void_p), ("peer_end", C.c_void_p)]
+
+
+class WindowFrame(C.Structure):
+    """dbhip_window_frame"""
+    _fields_ = [("units", C.c_int32), ("start_kind", C.c_int32), ("end_kind", C.c_int32), ("_pad", C.c_int32),
+                ("start_offset", C.c_int64), ("end_offset", C.c_int64)]
+
+
+WIN_ROWS, WIN_RANGE = 0, 1
+WIN_UNBOUNDED_PRECEDING, WIN_PRECEDING, WIN_CURRENT_ROW, WIN_FOLLOWING, WIN_UNBOUNDED_FOLLOWING = range(5)
+WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK, WIN_PERCENT_RANK, WIN_CUME_DIST, WIN_NTILE = range(6)
+WIN_FIRST_VALUE, WIN_LAST_VALUE, WIN_NTH_VALUE = range(3)
+
+
 def library_path():
     # DBHIP_LIBRARY: another build of the same library (same-box A/B runs against an older commit's build)
     return os.environ.get("DBHIP_LIBRARY") or os.path.join(_HERE, "libdbhip.so")
@@ -103,7 +120,8 @@ SYMBOLS = [
     "dbhip_join_add_build_binary", "dbhip_join_finalize_binary", "dbhip_join_probe_count_binary", "dbhip_join_probe_binary", "dbhip_join_destroy_binary",
     "dbhip_join_create", "dbhip_join_create_keys", "dbhip_join_probe_mark",
     "dbhip_join_add_build", "dbhip_join_finalize", "dbhip_join_probe_count", "dbhip_join_probe",
-    "dbhip_join_destroy", "dbhip_join_mark_build", "dbhip_join_build_matched", "dbhip_sort_perm", "dbhip_merge_sorted_perm", "dbhip_sort_bound_partition", "dbhip_bitmap_set_indices", "dbhip_siphash64", "dbhip_scatter_indices", "dbhip_scatter_block", "dbhip_vec_distance", "dbhip_vec_distance_rows", "dbhip_vec_topk", "dbhip_score_u8",
+    "dbhip_join_destroy", "dbhip_join_mark_build", "dbhip_join_build_matched", "dbhip_sort_perm", "dbhip_merge_sorted_perm", "dbhip_sort_bound_partition",
+    "dbhip_window_bounds", "dbhip_window_rank", "dbhip_window_shift", "dbhip_window_value", "dbhip_window_aggregate", "dbhip_bitmap_set_indices", "dbhip_siphash64", "dbhip_scatter_indices", "dbhip_scatter_block", "dbhip_vec_distance", "dbhip_vec_distance_rows", "dbhip_vec_topk", "dbhip_score_u8",
     "dbhip_vec_topk_merge", "dbhip_vec_index_build", "dbhip_vec_index_search", "dbhip_vec_index_destroy",
     "dbhip_comm_unique_id", "dbhip_comm_create", "dbhip_comm_destroy", "dbhip_comm_abort", "dbhip_comm_allgather", "dbhip_comm_alltoall",
     "dbhip_comm_allreduce_sum_u64", "dbhip_groupby_exchange_allgather", "dbhip_groupby_exchange_alltoall", "dbhip_kmeans", "dbhip_vec_kernel_f32", "dbhip_hnsw_build", "dbhip_hnsw_build_sequential", "dbhip_hnsw_from_graph", "dbhip_hnsw_open", "dbhip_hnsw_export_graph", "dbhip_hnsw_search", "dbhip_hnsw_scores",

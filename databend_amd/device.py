@@ -1582,6 +1582,103 @@ def merge_sorted_perm(cols, run_offsets, desc=None, nulls_first=None, limit=0):
     return out.to_numpy(np.uint32, m)
 
 
+def WindowFrame(units, start, end):
+    """dbhip_window_frame: units = L.WIN_ROWS / L.WIN_RANGE; start, end = a bound kind (L.WIN_UNBOUNDED_PRECEDING, L.WIN_CURRENT_ROW,
+    L.WIN_UNBOUNDED_FOLLOWING) or (L.WIN_PRECEDING / L.WIN_FOLLOWING, offset)"""
+    f = L.WindowFrame()
+    f.units = int(units)
+    sk, so = start if isinstance(start, (tuple, list)) else (start, 0)
+    ek, eo = end if isinstance(end, (tuple, list)) else (end, 0)
+    f.start_kind, f.start_offset, f.end_kind, f.end_offset = int(sk), int(so), int(ek), int(eo)
+    return f
+
+
+class Window:
+    """TransformWindow over one sorted block (include/dbhip.h a19): the columns are already ordered by (partition keys, order keys).
+    dbhip_window_bounds runs once; the four boundary arrays stay in HBM and every function call reads them.
+    The value-returning methods give (values, validity) on the host, or with device=True the HBM-resident Column; `out` /
+    `out_validity` (DeviceBuffers of the result's size / ceil(n/64)*8 bytes) are written instead of fresh allocations when given."""
+
+    def __init__(self, partition_cols, order_cols, n=None, stream=None):
+        partition_cols, order_cols = list(partition_cols), list(order_cols)
+        self.n = int(n if n is not None else (partition_cols + order_cols)[0].n)
+        self.stream = stream
+        self._keep = (partition_cols, order_cols)      # the call below is asynchronous: the key columns live as long as the window
+        self._arrays = [DeviceBuffer(max(self.n, 1) * 4) for _ in range(4)]
+        self.rows = L.WindowRows()
+        self.rows.n = self.n
+        self.rows.part_start, self.rows.part_end, self.rows.peer_start, self.rows.peer_end = [b.ptr for b in self._arrays]
+        check(lib().dbhip_window_bounds(_cols(partition_cols) if partition_cols else None, len(partition_cols), _cols(order_cols) if order_cols else None,
+                                        len(order_cols), C.c_int64(self.n), C.byref(self.rows), stream))
+
+    def bounds(self):
+        """-> part_start, part_end, peer_start, peer_end (numpy u32)"""
+        check(lib().dbhip_stream_sync(self.stream))
+        return tuple(b.to_numpy(np.uint32, self.n) for b in self._arrays)
+
+    def _bitmap(self, given):
+        return given if given is not None else DeviceBuffer(((self.n + 63) // 64) * 8 + 8)
+
+    def _finish(self, col, device):
+        if device:
+            return col
+        check(lib().dbhip_stream_sync(self.stream))
+        if col.dtype == L.T_STRING:
+            vals = col.string_values() if col.buffers is not None else view_strings(col.to_numpy())
+        else:
+            vals = col.to_numpy()
+        return vals, col.validity_numpy()
+
+    def rank(self, kind, buckets=0, out=None, device=False):
+        """row_number / rank / dense_rank / ntile -> u64, percent_rank / cume_dist -> f64 (numpy, or the DeviceBuffer with device=True)"""
+        out = out if out is not None else DeviceBuffer(max(self.n, 1) * 8)
+        check(lib().dbhip_window_rank(C.byref(self.rows), int(kind), C.c_uint64(int(buckets)), C.c_void_p(out.ptr), self.stream))
+        if device:
+            return out
+        check(lib().dbhip_stream_sync(self.stream))
+        return out.to_numpy(np.float64 if kind in (L.WIN_PERCENT_RANK, L.WIN_CUME_DIST) else np.uint64, self.n)
+
+    def _value_out(self, col, out):
+        if out is not None:
+            return out
+        return DeviceBuffer(((self.n + 63) // 64) * 8 + 8 if col.dtype == L.T_BOOL else max(self.n, 1) * ELEM_SIZE[col.dtype] + 64)
+
+    def shift(self, col, offset, default=None, out=None, out_validity=None, device=False):
+        """lag (offset < 0) / lead (offset > 0); default = None (NULL), a Column read at the row, or a Column.scalar"""
+        out, vb = self._value_out(col, out), self._bitmap(out_validity)
+        dc = default.c() if default is not None else None
+        check(lib().dbhip_window_shift(C.byref(self.rows), C.byref(col.c()), C.c_int64(int(offset)), C.byref(dc) if dc is not None else None,
+                                       C.c_void_p(out.ptr), C.c_void_p(vb.ptr), self.stream))
+        res = Column(col.dtype, self.n, out, vb, col.precision, col.scale, buffers=col.buffers, keep=(col, default))
+        res.n_buffers = col.n_buffers
+        return self._finish(res, device)
+
+    def value(self, kind, col, frame, nth=1, out=None, out_validity=None, device=False):
+        """first_value / last_value / nth_value over the frame"""
+        out, vb = self._value_out(col, out), self._bitmap(out_validity)
+        check(lib().dbhip_window_value(C.byref(self.rows), int(kind), C.c_int64(int(nth)), C.byref(col.c()), C.byref(frame), C.c_void_p(out.ptr),
+                                       C.c_void_p(vb.ptr), self.stream))
+        res = Column(col.dtype, self.n, out, vb, col.precision, col.scale, buffers=col.buffers, keep=(col,))
+        res.n_buffers = col.n_buffers
+        return self._finish(res, device)
+
+    def aggregate(self, kind, col, frame, out=None, out_validity=None, device=False):
+        """COUNT / SUM / MIN / MAX over the frame; col = None is count(*). The result has the type of dbhip_groupby_result_type."""
+        d = AggDesc()
+        d.kind = int(kind)
+        if col is not None:
+            d.arg_type, d.arg_precision, d.arg_scale, d.arg_nullable = col.dtype, col.precision, col.scale, 1 if col.validity is not None else 0
+        else:
+            d.arg_type = L.T_U64
+        t, p, sc = C.c_int32(), C.c_uint8(), C.c_uint8()
+        check(lib().dbhip_groupby_result_type(C.byref(d), C.byref(t), C.byref(p), C.byref(sc)))
+        out = out if out is not None else DeviceBuffer(max(self.n, 1) * ELEM_SIZE.get(t.value, 16) + 64)
+        vb = self._bitmap(out_validity)
+        check(lib().dbhip_window_aggregate(C.byref(self.rows), C.byref(d), C.byref(col.c()) if col is not None else None, C.byref(frame), C.c_void_p(out.ptr),
+                                           C.c_void_p(vb.ptr), self.stream))
+        return self._finish(Column(t.value, self.n, out, vb, p.value, sc.value, keep=(col,)), device)
+
+
 class VectorColumn:
     """Flat row-major f32 vectors in HBM (VectorColumn::Float32, types/vector.rs:377-380)."""
 

@@ -762,6 +762,79 @@ int32_t dbhip_sort_bound_partition(const dbhip_col* keys, const dbhip_col* bound
                                    const uint8_t* nulls_first_host, int32_t nkeys, int64_t n, int64_t nbounds,
                                    uint32_t* out_part, uint64_t* out_counts, void* stream);
 
+/* jit-embed: skip (the run-time compiled kernels never see this group: csrc/Makefile cuts it from the header text it embeds) */
+/* ---- a19: window -------------------------------------------------------------------
+ * Replaces TransformWindow (src/query/service/src/pipelines/processors/transforms/window/transform_window.rs, window_function.rs,
+ * frame_bound.rs) over ONE sorted input, like dbhip_sort_perm: the rows are already ordered by (partition keys, order keys) — the
+ * block dbhip_sort_perm + dbhip_take_block produce — and the binding squashes blocks first. Row positions
+ * are u32. All five calls are asynchronous on `stream` (dbhip_window_bounds with a String key and the gated Decimal128 sum read one
+ * word back), take their scratch from the (thread, stream) scratch and poll cancellation between launches; a refused shape returns
+ * its code before anything is launched and leaves the stream usable.
+ *
+ * dbhip_window_bounds fills the four per-row arrays. Two neighbouring rows belong to one partition when they tie on every partition
+ * key in the sense of dbhip_sort_perm: NULL ties with NULL, every NaN is one value, -0.0 ties with +0.0, Strings tie by length and
+ * bytes (any length: equality needs no 4096-byte limit; values beyond 12 bytes need the column's `buffers` and a buffer index below `n_buffers`, else DBHIP_ERR_INVALID).
+ * Rows are peers when they are in one partition and tie on every order key. Key types: those of dbhip_sort_perm, up to 8 + 8
+ * columns (others: DBHIP_ERR_UNSUPPORTED). n_partition = 0: one partition of everything; n_order = 0: every row of a partition is a
+ * peer of every other; n = 0: DBHIP_OK; n > 2^32 - 2: DBHIP_ERR_INVALID. rows->n is set to n.
+ * Boolean values (keys and arguments of this group) are read from bit 0 of `data`, as everywhere but dbhip_concat_columns: dbhip_col has a bit
+ * offset for the validity only, so the binding materialises a sliced Boolean column first.
+ *
+ * The frame of row i is [lo, hi). ROWS: lo = part_start for UNBOUNDED PRECEDING, else i - k, i, i + k; hi = part_end for UNBOUNDED
+ * FOLLOWING, else i - k + 1, i + 1, i + k + 1. RANGE takes UNBOUNDED and CURRENT ROW bounds only — CURRENT ROW as a start is
+ * peer_start, as an end peer_end; RANGE with an offset is DBHIP_ERR_UNSUPPORTED (it needs arithmetic on the order key: the binding
+ * keeps the CPU operator). Both ends are clamped into [part_start, part_end]; hi <= lo is an empty frame. Offsets are 0 .. INT64_MAX
+ * (2^62 does not overflow the index arithmetic). DBHIP_ERR_INVALID: a negative offset, UNBOUNDED FOLLOWING as a start, UNBOUNDED
+ * PRECEDING as an end, a start kind after the end kind, k PRECEDING .. m PRECEDING with k < m, k FOLLOWING .. m FOLLOWING with k > m.
+ * Out of scope: RANGE offsets, IGNORE NULLS, EXCLUDE, partitions that span calls. */
+typedef struct {            /* per-row boundaries, device arrays of n u32, owned by the caller */
+  int64_t n;
+  uint32_t* part_start;     /* first row of row i's partition                      */
+  uint32_t* part_end;       /* one past its last row                               */
+  uint32_t* peer_start;     /* first row of row i's peer group (equal order keys)  */
+  uint32_t* peer_end;       /* one past its last peer                              */
+} dbhip_window_rows;
+
+typedef enum { DBHIP_WIN_ROWS = 0, DBHIP_WIN_RANGE = 1 } dbhip_window_units;
+typedef enum { DBHIP_WIN_UNBOUNDED_PRECEDING = 0, DBHIP_WIN_PRECEDING = 1, DBHIP_WIN_CURRENT_ROW = 2,
+               DBHIP_WIN_FOLLOWING = 3, DBHIP_WIN_UNBOUNDED_FOLLOWING = 4 } dbhip_window_bound;
+typedef struct { int32_t units, start_kind, end_kind, _pad; int64_t start_offset, end_offset; } dbhip_window_frame;
+
+typedef enum { DBHIP_WIN_ROW_NUMBER = 0, DBHIP_WIN_RANK = 1, DBHIP_WIN_DENSE_RANK = 2, DBHIP_WIN_PERCENT_RANK = 3,
+               DBHIP_WIN_CUME_DIST = 4, DBHIP_WIN_NTILE = 5 } dbhip_window_rank_kind;
+typedef enum { DBHIP_WIN_FIRST_VALUE = 0, DBHIP_WIN_LAST_VALUE = 1, DBHIP_WIN_NTH_VALUE = 2 } dbhip_window_value_kind;
+
+int32_t dbhip_window_bounds(const dbhip_col* partition_keys, int32_t n_partition, const dbhip_col* order_keys, int32_t n_order,
+                            int64_t n, dbhip_window_rows* rows, void* stream);
+/* `out` = n UInt64: row_number = i - part_start + 1; rank = peer_start - part_start + 1; dense_rank = peer groups begun in
+ * [part_start, i]; ntile(buckets): rows = part_end - part_start, k = i - part_start, q, r = divmod(rows, buckets), k / (q + 1) + 1
+ * when k < r (q + 1), else (k - r (q + 1)) / q + r + 1 (buckets = 0: DBHIP_ERR_INVALID). `out` = n Float64: percent_rank =
+ * (rank - 1) / (rows - 1), 0.0 for a one-row partition; cume_dist = (peer_end - part_start) / rows — one IEEE double division of
+ * exact integers each, so both are bit-exact. */
+int32_t dbhip_window_rank(const dbhip_window_rows* rows, int32_t kind, uint64_t buckets, void* out, void* stream);
+/* lag / lead: offset < 0 is lag(|offset|), > 0 lead, 0 the row itself. out[i] = arg[i + offset] with its validity when that row
+ * lies in the partition, otherwise `dflt` — a column read at row i or a scalar, of the argument's type — or NULL when dflt = NULL.
+ * Every fixed-width type including DEC256, BOOL (`out` is a Bitmap of ceil(n/64)*8 bytes) and STRING (views are copied, the data
+ * buffers are shared with the source as with dbhip_take; a STRING default is DBHIP_ERR_UNSUPPORTED: the two buffer tables differ).
+ * out_validity (required): ceil(n/64)*8 bytes. Values under a NULL result are zero. */
+int32_t dbhip_window_shift(const dbhip_window_rows* rows, const dbhip_col* arg, int64_t offset, const dbhip_col* dflt,
+                           void* out, uint8_t* out_validity, void* stream);
+/* first_value = arg[lo], last_value = arg[hi - 1], nth_value = arg[lo + nth - 1] (nth >= 1, else DBHIP_ERR_INVALID); NULL when the
+ * frame is empty, when that row lies past hi, or when the source row is NULL. RESPECT NULLS only. Types and buffers as for shift. */
+int32_t dbhip_window_value(const dbhip_window_rows* rows, int32_t kind, int64_t nth, const dbhip_col* arg,
+                           const dbhip_window_frame* frame, void* out, uint8_t* out_validity, void* stream);
+/* An aggregate over every row's frame; `out` has the type dbhip_groupby_result_type gives for `agg`. COUNT: count(*) when arg is
+ * NULL, else the valid rows of the frame; UInt64, never NULL. SUM: integers to i64 / u64 wrapping, f32 / f64 to f64 (an f32 is
+ * widened first), DEC64 as in the aggregation (i64 wrapping); DEC128 with agg->arg_precision > 18 only when the sum of |x| of every
+ * partition stays inside +-(10^38 - 1), so that no prefix and no frame can leave the range — otherwise DBHIP_ERR_UNSUPPORTED (the CPU
+ * operator raises the overflow itself); DEC256: DBHIP_ERR_UNSUPPORTED. MIN / MAX: numbers, Date, Timestamp, DEC64, DEC128, floats as
+ * OrderedFloat; BOOL, String, DEC256: DBHIP_ERR_UNSUPPORTED. SUM / MIN / MAX are NULL (validity bit 0, value 0) when the frame is
+ * empty or holds no valid row. The value under a NULL argument row never reaches a result. A float SUM adds the frame's own terms
+ * only (a NaN or an Inf before the frame does not reach it). out_validity (required): ceil(n/64)*8 bytes. */
+int32_t dbhip_window_aggregate(const dbhip_window_rows* rows, const dbhip_agg_desc* agg, const dbhip_col* arg,
+                               const dbhip_window_frame* frame, void* out, uint8_t* out_validity, void* stream);
+/* jit-embed: resume */
+
 /* ---- a17/a18: vector distance ------------------------------------------------
  * Replaces cosine_distance / l2_distance / inner_product / l1_distance
  * (src/common/vector/src/distance.rs:19-165) driven by
