@@ -82,12 +82,20 @@ pub const DBHIP_WIN_NTILE: i32 = 5;   // dbhip_window_rank_kind
 pub const DBHIP_WIN_FIRST_VALUE: i32 = 0;   // dbhip_window_value_kind
 pub const DBHIP_WIN_LAST_VALUE: i32 = 1;   // dbhip_window_value_kind
 pub const DBHIP_WIN_NTH_VALUE: i32 = 2;   // dbhip_window_value_kind
+pub const DBHIP_LIKE_EQUALS: i32 = 0;   // dbhip_like_kind_t
+pub const DBHIP_LIKE_PREFIX: i32 = 1;   // dbhip_like_kind_t
+pub const DBHIP_LIKE_SUFFIX: i32 = 2;   // dbhip_like_kind_t
+pub const DBHIP_LIKE_CONTAINS: i32 = 3;   // dbhip_like_kind_t
+pub const DBHIP_LIKE_SEGMENTS: i32 = 4;   // dbhip_like_kind_t
+pub const DBHIP_LIKE_NEGATE: i32 = 1;
+pub const DBHIP_LIKE_UNIT_BYTE: i32 = 2;
 pub const DBHIP_VEC_COSINE: i32 = 0;   // dbhip_vec_metric
 pub const DBHIP_VEC_L2: i32 = 1;   // dbhip_vec_metric
 pub const DBHIP_VEC_DOT: i32 = 2;   // dbhip_vec_metric
 pub const DBHIP_VEC_L1: i32 = 3;   // dbhip_vec_metric
 pub const DBHIP_VEC_NORM: i32 = 4;   // dbhip_vec_metric
 pub const DBHIP_ABI_VERSION: i32 = 6;
+pub const DBHIP_LIKE_LONG_BYTES: i32 = 256;
 
 #[repr(C)]
 pub struct dbhip_groupby { _private: [u8; 0] }
@@ -317,6 +325,9 @@ extern "C" {
     pub fn dbhip_window_shift(rows: *const dbhip_window_rows, arg: *const dbhip_col, offset: i64, dflt: *const dbhip_col, out: *mut c_void, out_validity: *mut u8, stream: *mut c_void) -> i32;
     pub fn dbhip_window_value(rows: *const dbhip_window_rows, kind: i32, nth: i64, arg: *const dbhip_col, frame: *const dbhip_window_frame, out: *mut c_void, out_validity: *mut u8, stream: *mut c_void) -> i32;
     pub fn dbhip_window_aggregate(rows: *const dbhip_window_rows, agg: *const dbhip_agg_desc, arg: *const dbhip_col, frame: *const dbhip_window_frame, out: *mut c_void, out_validity: *mut u8, stream: *mut c_void) -> i32;
+    pub fn dbhip_like_kind(pattern_host: *const u8, pattern_len: i32, escape: i32) -> i32;
+    pub fn dbhip_like(col: *const dbhip_col, pattern_host: *const u8, pattern_len: i32, escape: i32, flags: i32, n: i64, out_bitmap: *mut u8, stream: *mut c_void) -> i32;
+    pub fn dbhip_str_match(kind: i32, col: *const dbhip_col, needle_host: *const u8, needle_len: i32, flags: i32, n: i64, out_bitmap: *mut u8, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_distance_rows(metric: i32, elem_type: i32, lhs: *const c_void, lhs_is_scalar: i32, rhs: *const c_void, rhs_is_scalar: i32, n: i64, dim: i32, out: *mut c_void, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_distance(metric: i32, base: *const f32, n: i64, dim: i32, queries: *const f32, nq: i32, out: *mut f32, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_topk(metric: i32, base: *const f32, n: i64, dim: i32, queries: *const f32, nq: i32, k: i32, out_idx: *mut u32, out_dist: *mut f32, stream: *mut c_void) -> i32;

@@ -96,6 +96,11 @@ WIN_UNBOUNDED_PRECEDING, WIN_PRECEDING, WIN_CURRENT_ROW, WIN_FOLLOWING, WIN_UNBO
 WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK, WIN_PERCENT_RANK, WIN_CUME_DIST, WIN_NTILE = range(6)
 WIN_FIRST_VALUE, WIN_LAST_VALUE, WIN_NTH_VALUE = range(3)
 
+# dbhip_like_kind_t, the flags of dbhip_like / dbhip_str_match, and DBHIP_LIKE_LONG_BYTES
+LIKE_EQUALS, LIKE_PREFIX, LIKE_SUFFIX, LIKE_CONTAINS, LIKE_SEGMENTS = range(5)
+LIKE_NEGATE, LIKE_UNIT_BYTE = 1, 2
+LIKE_LONG_BYTES = 256
+
 
 def library_path():
     # DBHIP_LIBRARY: another build of the same library (same-box A/B runs against an older commit's build)
@@ -121,7 +126,8 @@ SYMBOLS = [
     "dbhip_join_create", "dbhip_join_create_keys", "dbhip_join_probe_mark",
     "dbhip_join_add_build", "dbhip_join_finalize", "dbhip_join_probe_count", "dbhip_join_probe",
     "dbhip_join_destroy", "dbhip_join_mark_build", "dbhip_join_build_matched", "dbhip_sort_perm", "dbhip_merge_sorted_perm", "dbhip_sort_bound_partition",
-    "dbhip_window_bounds", "dbhip_window_rank", "dbhip_window_shift", "dbhip_window_value", "dbhip_window_aggregate", "dbhip_bitmap_set_indices", "dbhip_siphash64", "dbhip_scatter_indices", "dbhip_scatter_block", "dbhip_vec_distance", "dbhip_vec_distance_rows", "dbhip_vec_topk", "dbhip_score_u8",
+    "dbhip_window_bounds", "dbhip_window_rank", "dbhip_window_shift", "dbhip_window_value", "dbhip_window_aggregate",
+    "dbhip_like_kind", "dbhip_like", "dbhip_str_match", "dbhip_bitmap_set_indices", "dbhip_siphash64", "dbhip_scatter_indices", "dbhip_scatter_block", "dbhip_vec_distance", "dbhip_vec_distance_rows", "dbhip_vec_topk", "dbhip_score_u8",
     "dbhip_vec_topk_merge", "dbhip_vec_index_build", "dbhip_vec_index_search", "dbhip_vec_index_destroy",
     "dbhip_comm_unique_id", "dbhip_comm_create", "dbhip_comm_destroy", "dbhip_comm_abort", "dbhip_comm_allgather", "dbhip_comm_alltoall",
     "dbhip_comm_allreduce_sum_u64", "dbhip_groupby_exchange_allgather", "dbhip_groupby_exchange_alltoall", "dbhip_kmeans", "dbhip_vec_kernel_f32", "dbhip_hnsw_build", "dbhip_hnsw_build_sequential", "dbhip_hnsw_from_graph", "dbhip_hnsw_open", "dbhip_hnsw_export_graph", "dbhip_hnsw_search", "dbhip_hnsw_scores",
@@ -152,6 +158,10 @@ def load_library():
         fn = getattr(L, name)
         if name != "dbhip_last_error":
             fn.restype = C.c_int64 if name in _RESTYPE_I64 else C.c_int32
+    # the LIKE group: (pattern, len, escape) / (col, pattern, len, escape, flags, n, out, stream) / (kind, col, needle, len, flags, n, out, stream)
+    L.dbhip_like_kind.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+    L.dbhip_like.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
+    L.dbhip_str_match.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
     _LIB = L
     return L
 

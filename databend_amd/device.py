@@ -479,6 +479,70 @@ def bitmap_count(pred, n):
     return int(out.to_numpy(np.uint64, 1)[0])
 
 
+def _escape_byte(escape):
+    """b"\\\\" / "!" / 0x21 -> the byte's value; None or b"" -> -1 (no escape)"""
+    if escape is None or escape == b"" or escape == "":
+        return -1
+    if isinstance(escape, str):
+        escape = escape.encode()
+    if isinstance(escape, (bytes, bytearray)):
+        if len(escape) != 1:
+            raise ValueError("the escape is one byte")
+        return escape[0]
+    return int(escape)
+
+
+def _host_bytes(b):
+    b = b.encode() if isinstance(b, str) else bytes(b)
+    return (C.c_uint8 * max(len(b), 1)).from_buffer_copy(b or b"\0"), len(b)
+
+
+def like_kind(pattern, escape=b"\\"):
+    """dbhip_like_kind: L.LIKE_EQUALS / _PREFIX / _SUFFIX / _CONTAINS / _SEGMENTS of a constant pattern (host only, no device needed);
+    raises DbhipError for a pattern the device call refuses"""
+    buf, ln = _host_bytes(pattern)
+    k = lib().dbhip_like_kind(buf, C.c_int32(ln), C.c_int32(_escape_byte(escape)))
+    if k < 0:
+        check(-k)
+    return k
+
+
+def _match_out(col, n):
+    n = col.n if n is None else n
+    return n, DeviceBuffer(((n + 63) // 64) * 8 + 8)
+
+
+def _match_result(col, n, out):
+    """the Boolean result of a string predicate: the column's own validity Bitmap, at its bit offset"""
+    if col.is_scalar:
+        return Column(L.T_BOOL, n, out, _merged_validity(col, col, n), keep=(col,))
+    res = Column(L.T_BOOL, n, out, col.validity, keep=(col,))
+    res.voff = col.voff
+    return res
+
+
+def like(col, pattern, escape=b"\\", negate=False, unit_byte=False, n=None):
+    """col LIKE pattern (NOT LIKE with negate) for a constant pattern -> Boolean Column that keeps col.validity. The bit under a NULL row
+    is 0 either way, so the values alone are the filter. unit_byte: `_` reads one byte instead of one UTF-8 unit."""
+    n, out = _match_out(col, n)
+    buf, ln = _host_bytes(pattern)
+    flags = (L.LIKE_NEGATE if negate else 0) | (L.LIKE_UNIT_BYTE if unit_byte else 0)
+    cc = col.c()
+    check(lib().dbhip_like(C.byref(cc), buf, C.c_int32(ln), C.c_int32(_escape_byte(escape)), C.c_int32(flags), C.c_int64(n), C.c_void_p(out.ptr), None))
+    return _match_result(col, n, out)
+
+
+def str_match(kind, col, needle, negate=False, n=None):
+    """starts_with (L.LIKE_PREFIX) / ends_with (L.LIKE_SUFFIX) / position(needle in col) > 0 (L.LIKE_CONTAINS) / equality (L.LIKE_EQUALS)
+    with a literal needle -> Boolean Column that keeps col.validity"""
+    n, out = _match_out(col, n)
+    buf, ln = _host_bytes(needle)
+    cc = col.c()
+    check(lib().dbhip_str_match(C.c_int32(kind), C.byref(cc), buf, C.c_int32(ln), C.c_int32(L.LIKE_NEGATE if negate else 0), C.c_int64(n),
+                                C.c_void_p(out.ptr), None))
+    return _match_result(col, n, out)
+
+
 def select_cmp(op, a, b, sel=None, n=None, want_false=False):
     """Selector leaf (filter/select_value): `a op b` evaluated on the rows of `sel` (a DeviceBuffer of u32 row ids, `n` of them) or on
     all n rows; -> (true list DeviceBuffer, n_true, false list DeviceBuffer | None). NULL rows do not pass."""

@@ -835,6 +835,63 @@ int32_t dbhip_window_aggregate(const dbhip_window_rows* rows, const dbhip_agg_de
                                const dbhip_window_frame* frame, void* out, uint8_t* out_validity, void* stream);
 /* jit-embed: resume */
 
+/* jit-embed: skip (as a19: the run-time compiled kernels never see this group) */
+/* ---- a20: LIKE and substring predicates over String columns ------------------------
+ * Replaces the closures of register_like / generate_like_pattern (src/query/functions/src/scalars/comparison.rs,
+ * LikePattern::{OrdinalStr, StartOfPercent, EndOfPercent, SurroundByPercent, SimplePattern, ComplexPattern}) for a CONSTANT pattern,
+ * and starts_with / ends_with / position(needle in col) > 0 (dbhip_str_match).
+ *
+ * Pattern grammar. `escape` is a byte 0..255, or -1 for none (the reference's default is `\`). An escape byte followed by any byte
+ * makes that byte a literal; an escape byte as the LAST byte of the pattern is itself a literal. An unescaped `%` matches any run of
+ * bytes, the empty run included. An unescaped `_` matches exactly one unit. Every other byte matches itself: matching is case
+ * sensitive and has no collation.
+ *
+ * Units. With DBHIP_LIKE_UNIT_BYTE a unit is one byte. Otherwise the unit boundaries of a value are position 0, position len and every
+ * position i whose byte is not of the form 10xxxxxx, and a unit runs from one boundary to the next: one code point on valid UTF-8,
+ * and still well defined on arbitrary bytes. The binding picks the mode of its reference version.
+ *
+ * Match and kinds. The WHOLE value must match. After parsing, the pattern is a list of segments: maximal runs of literal bytes and
+ * `_`, separated by one or more `%`. The first segment is anchored at the start unless the pattern begins with `%`, the last one at
+ * the end unless the pattern ends with `%`. dbhip_like_kind: EQUALS = one segment anchored at both ends and no `_`; PREFIX / SUFFIX /
+ * CONTAINS = one segment without `_` with `%` behind it / in front of it / on both sides; SEGMENTS = everything else, the all-`%`
+ * pattern (matches every non-NULL row) and the empty pattern (matches only the empty value) included.
+ *
+ * Limits. pattern_len <= 255 and at most 16 segments, else DBHIP_ERR_UNSUPPORTED before any launch (keep the CPU closure). A negative
+ * length or an escape outside -1..255 is DBHIP_ERR_INVALID; so are flag bits other than the two below and n above 2^32 - 2.
+ *
+ * Column. `col` must be DBHIP_T_STRING (else DBHIP_ERR_INVALID), its views 16-byte aligned. is_scalar is allowed: one value decides
+ * every row. validity_offset is honoured. A NULL row is not dereferenced and its bit is 0, also under DBHIP_LIKE_NEGATE: a NULL as a
+ * filter is FALSE; the caller keeps the validity for a value result. A long view (more than 12 bytes) whose buffer index is >=
+ * n_buffers (or whose buffer pointer is NULL) is never dereferenced; its bit is 0. Value bytes are read only with naturally aligned
+ * 4-byte (pass 1) and 1-byte (pass 2) loads that each cover at least one byte of the value, so nothing beyond the pages a value
+ * occupies is touched: data buffers need no padding.
+ *
+ * Output. out_bitmap: LSB-first, written as whole 64-bit words: ceil(n/64)*8 bytes, 8-byte aligned, bits past n zero — as
+ * dbhip_filter_select, dbhip_bitmap_binary and dbhip_groupby_add_block_filtered take it.
+ *
+ * Calls. n = 0 returns DBHIP_OK. Asynchronous on `stream`; scratch comes from the (thread, stream) scratch; cancellation is polled
+ * between the launches. Values longer than DBHIP_LIKE_LONG_BYTES that need a search (CONTAINS, SEGMENTS) are handed from the
+ * lane-per-row pass to a wave-per-row pass through a row list in scratch (4 bytes per row of the call); the second pass reads the
+ * list's length on the device.
+ * Out of scope (DBHIP_ERR_UNSUPPORTED or not expressible): a pattern that is a column, ILIKE and collations, REGEXP / RLIKE, a
+ * selection-vector form, patterns beyond the limits. */
+typedef enum { DBHIP_LIKE_EQUALS = 0, DBHIP_LIKE_PREFIX = 1, DBHIP_LIKE_SUFFIX = 2, DBHIP_LIKE_CONTAINS = 3,
+               DBHIP_LIKE_SEGMENTS = 4 } dbhip_like_kind_t;
+enum { DBHIP_LIKE_NEGATE = 1,      /* NOT LIKE: the bit of every non-NULL row is inverted */
+       DBHIP_LIKE_UNIT_BYTE = 2 }; /* `_` consumes one byte; default: one UTF-8 unit (above) */
+#define DBHIP_LIKE_LONG_BYTES 256  /* values longer than this take the wave-per-row pass */
+
+/* host only, needs no device and no dbhip_init: classifies a pattern; returns the kind or a negative -DBHIP_ERR_* */
+int32_t dbhip_like_kind(const uint8_t* pattern_host, int32_t pattern_len, int32_t escape);
+int32_t dbhip_like(const dbhip_col* col, const uint8_t* pattern_host, int32_t pattern_len, int32_t escape, int32_t flags,
+                   int64_t n, uint8_t* out_bitmap, void* stream);
+/* starts_with / ends_with / position(needle in col) > 0: `kind` is PREFIX / SUFFIX / CONTAINS / EQUALS, the needle is taken
+ * literally (no wildcard, no escape); same kernels, same output. An empty needle is a prefix, a suffix and a part of every value and
+ * equal to the empty one. needle_len <= 255. */
+int32_t dbhip_str_match(int32_t kind, const dbhip_col* col, const uint8_t* needle_host, int32_t needle_len, int32_t flags,
+                        int64_t n, uint8_t* out_bitmap, void* stream);
+/* jit-embed: resume */
+
 /* ---- a17/a18: vector distance ------------------------------------------------
  * Replaces cosine_distance / l2_distance / inner_product / l1_distance
  * (src/common/vector/src/distance.rs:19-165) driven by
