@@ -155,13 +155,7 @@ __device__ __forceinline__ fa_u32x4 fa_key_raw(const void* p, int type, int64_t 
 __device__ __forceinline__ bool fa_key_canon(int type, fa_u32x4 r, bool valid, uint64_t (&w)[2]) {
   bool ok = true;
   if (type == DBHIP_T_STRING) {
-    const uint32_t len = r.x;
-    const uint32_t m1 = len >= 4 ? 0xffffffffu : (len == 0 ? 0u : (0xffffffffu >> (8 * (4 - len))));
-    const uint32_t m2 = len >= 8 ? 0xffffffffu : (len <= 4 ? 0u : (0xffffffffu >> (8 * (8 - len))));
-    const uint32_t m3 = len >= 12 ? 0xffffffffu : (len <= 8 ? 0u : (0xffffffffu >> (8 * (12 - len))));
-    w[0] = ((uint64_t)(r.y & m1) << 32) | len;
-    w[1] = ((uint64_t)(r.w & m3) << 32) | (r.z & m2);
-    ok = len <= 12;
+    ok = sv_key_words(r.x, r.y, r.z, r.w, w[0], w[1]);
   } else {
     w[0] = (uint64_t)r.x | ((uint64_t)r.y << 32);
     w[1] = type == DBHIP_T_DEC128 ? ((uint64_t)r.z | ((uint64_t)r.w << 32)) : 0;

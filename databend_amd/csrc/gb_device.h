@@ -2,6 +2,7 @@
 // (k_groupby.hip) and the fused Q1 pipeline (k_q1.hip).
 #pragma once
 #include "dev_common.h"
+#include "dev_strview.h"
 #include "gb_layout.h"
 
 // order-preserving u64 key for MIN/MAX states: signed ints flip the sign bit,
@@ -71,9 +72,10 @@ __device__ __forceinline__ bool gb_load_words(const GbCol& c, int64_t row, uint6
     case DBHIP_T_STRING: {
       const uint32_t* p = (const uint32_t*)c.data + 4 * j;
       uint32_t len = p[0];
-      if (len > 12) return false;
+      if (len > SV_INLINE_MAX) return false;
       uint32_t d1 = p[1], d2 = p[2], d3 = p[3];
-      // zero the bytes past len so equal strings are equal words
+      // zero the bytes past len so equal strings are equal words: sv_canon's mask (dev_strview.h) in its branching form, kept
+      // written out here and below because the helper costs the numeric-key kernels that share this function registers
       if (len < 4) { d1 &= (len == 0) ? 0u : (0xffffffffu >> (8 * (4 - len))); d2 = 0; d3 = 0; }
       else if (len < 8) { d2 &= (len == 4) ? 0u : (0xffffffffu >> (8 * (8 - len))); d3 = 0; }
       else if (len < 12) { d3 &= (len == 8) ? 0u : (0xffffffffu >> (8 * (12 - len))); }
@@ -152,9 +154,9 @@ __device__ __forceinline__ bool gb_load_words_n(const GbCol& c, const int64_t (&
 #pragma unroll
       for (int u = 0; u < N; ++u) {
         const uint32_t len = d0[u];
-        if (len > 12) { ok = false; continue; }
+        if (len > SV_INLINE_MAX) { ok = false; continue; }
         uint32_t a = d1[u], b = d2[u], cc = d3[u];
-        // zero the bytes past len so equal strings are equal words
+        // zero the bytes past len so equal strings are equal words (the branching form, as in gb_load_words)
         if (len < 4) { a &= (len == 0) ? 0u : (0xffffffffu >> (8 * (4 - len))); b = 0; cc = 0; }
         else if (len < 8) { b &= (len == 4) ? 0u : (0xffffffffu >> (8 * (8 - len))); cc = 0; }
         else if (len < 12) { cc &= (len == 8) ? 0u : (0xffffffffu >> (8 * (12 - len))); }
@@ -310,7 +312,7 @@ __device__ __forceinline__ void gb_minmax_wide_locked(bool is_min, uint64_t* dst
 // table's arena (gb_pin_strings_*, k_groupby.hip), so a state never outlives the bytes it refers to. Order: bytes, then length
 // (Rust's `str` / `[u8]` Ord).
 __device__ __forceinline__ uint32_t gb_str_byte(uint64_t w0, uint64_t w2, uint32_t len, uint32_t i) {
-  if (len <= 12) return (uint32_t)((i < 4 ? (w0 >> (32 + 8 * i)) : (w2 >> (8 * (i - 4)))) & 0xFFu);
+  if (sv_is_inline(len)) return (uint32_t)((i < 4 ? (w0 >> (32 + 8 * i)) : (w2 >> (8 * (i - 4)))) & 0xFFu);
   return ((const uint8_t*)w2)[i];
 }
 // -1 / 0 / 1

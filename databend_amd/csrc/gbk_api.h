@@ -535,7 +535,7 @@ __global__ __launch_bounds__(256) void gb_rebase_rows_kernel(GbLayout L, const u
       uint64_t* o = out + i * L.W;
       for (int k = 0; k < L.W; ++k) {
         uint64_t v = r[k];
-        if (k < L.nkey_words && ((L.str_w1_mask >> k) & 1) && (uint32_t)r[k - 1] > 12) {
+        if (k < L.nkey_words && ((L.str_w1_mask >> k) & 1) && (uint32_t)r[k - 1] > SV_INLINE_MAX) {
           v = (uint64_t)(arena + v);
           lb += ((uint32_t)r[k - 1] + 7) & ~7u;
         }

@@ -79,7 +79,7 @@ __global__ __launch_bounds__(256) void gb_pin_strings_kernel(GbLayout L, const u
       for (int k = 1; k < L.nkey_words; ++k) {
         if (!((L.str_w1_mask >> k) & 1)) continue;
         const uint32_t len = (uint32_t)r[k - 1];
-        if (len <= 12) continue;
+        if (sv_is_inline(len)) continue;
         const uint64_t room = ((uint64_t)len + 7) & ~7ULL;
         if (mode == 3) { mine += room; continue; }
         const uint64_t off = atomicAdd((unsigned long long*)&ctrl[8], (unsigned long long)room);
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256) void gb_pin_strings_kernel(GbLayout L, const u
       if (!gb_minmax_str(L, a)) continue;
       uint64_t* st = rows + sl * L.W + L.agg_off[a];
       const uint32_t len = (uint32_t)st[0];
-      if (!st[1] || len <= 12) continue;
+      if (!st[1] || sv_is_inline(len)) continue;
       const bool inside = st[2] >= lo && st[2] < hi;
       if (mode == 2) { if (inside) st[2] = (uint64_t)((int64_t)st[2] + delta); continue; }
       const uint64_t room = ((uint64_t)len + 7) & ~7ULL;

@@ -39,7 +39,7 @@ __global__ __launch_bounds__(256) void group_hash_kernel(HashCols hc, int64_t n,
           const bool valid = !hc.c[k].validity || bit_get(hc.c[k].validity, hc.c[k].voff + j);
           const uint32_t* v = (const uint32_t*)hc.c[k].data + 4 * j;
           const uint32_t len = v[0];
-          const uint8_t* p = len <= 12 ? (const uint8_t*)(v + 1) : (const uint8_t*)hc.c[k].buffers[v[2]] + v[3];
+          const uint8_t* p = sv_bytes(v, hc.c[k].buffers);
           const uint64_t hk = valid ? agg_hash_bytes(p, len) : DBHIP_NULL_HASH_VAL;
           h[u] = (k == 0) ? hk : merge_hash(h[u], hk);
         }
@@ -114,11 +114,11 @@ __global__ __launch_bounds__(256) void gb_serialize_kernel(GbLayout L, GbCols C,
           const uint32_t len = v[0];
           uint64_t ww[2] = {0, 0};
           hlong[u] = 0;
-          if (len <= 12 || !valid[u]) {
+          if (sv_is_inline(len) || !valid[u]) {
             bool vv;
             gb_load_words(kc, row[u], ww, &vv);
           } else {
-            const uint8_t* p = (const uint8_t*)kc.buffers[v[2]] + v[3];
+            const uint8_t* p = sv_bytes(v, kc.buffers);
             ww[0] = ((uint64_t)v[1] << 32) | len;
             ww[1] = (uint64_t)p;
             hlong[u] = agg_hash_bytes(p, len);
@@ -216,12 +216,12 @@ __global__ __launch_bounds__(256) void gb_serialize_kernel(GbLayout L, GbCols C,
           const uint32_t* v = (const uint32_t*)ac.data + 4 * j;
           const uint32_t len = v[0];
           uint64_t ww[2] = {0, 0};
-          if (len <= 12 || !valid[u]) {
+          if (sv_is_inline(len) || !valid[u]) {
             bool vv;
             gb_load_words(ac, row[u], ww, &vv);
           } else if (ac.buffers) {
             ww[0] = ((uint64_t)v[1] << 32) | len;
-            ww[1] = (uint64_t)((const uint8_t*)ac.buffers[v[2]] + v[3]);
+            ww[1] = (uint64_t)sv_bytes(v, ac.buffers);
           } else {
             atomicOr((unsigned long long*)&ctrl[3], 2ULL);   // a long view without data buffers
           }
@@ -276,7 +276,7 @@ __device__ __forceinline__ bool bytes_equal(const uint8_t* x, const uint8_t* y, 
 __device__ __forceinline__ bool keys_equal(const GbLayout& L, const uint64_t* a, const uint64_t* b, const uint8_t* arena) {
   bool eq = true;
   for (int k = 0; k < L.nkey_words; ++k) {
-    if (((L.str_w1_mask >> k) & 1) && (uint32_t)a[k - 1] > 12) {
+    if (((L.str_w1_mask >> k) & 1) && (uint32_t)a[k - 1] > SV_INLINE_MAX) {
       eq = eq && a[k - 1] == b[k - 1] && bytes_equal((const uint8_t*)a[k], arena + b[k], (uint32_t)a[k - 1]);
       continue;
     }
@@ -288,7 +288,7 @@ __device__ __forceinline__ bool keys_equal(const GbLayout& L, const uint64_t* a,
 // host made room for every long byte of the chunk before the launch)
 __device__ __forceinline__ void write_group_keys(const GbLayout& L, const uint64_t* r, uint64_t* d, uint8_t* arena, uint64_t* ctrl) {
   for (int k = 0; k < L.nkey_words; ++k) {
-    if (((L.str_w1_mask >> k) & 1) && (uint32_t)r[k - 1] > 12) {
+    if (((L.str_w1_mask >> k) & 1) && (uint32_t)r[k - 1] > SV_INLINE_MAX) {
       const uint32_t len = (uint32_t)r[k - 1];
       const unsigned long long off = atomicAdd((unsigned long long*)&ctrl[8], (unsigned long long)((len + 7) & ~7u));
       const uint8_t* src = (const uint8_t*)r[k];
@@ -727,7 +727,7 @@ __global__ __launch_bounds__(256) void gb_result_kernel(GbLayout L, const uint64
             if (L.key_type[k] == DBHIP_T_STRING) {
               // words -> 16-byte view: {len, bytes[12]} inline, or {len, prefix, buffer 0, offset} into the table's arena
               uint32_t* v = (uint32_t*)o + 4 * i;
-              if ((uint32_t)w0 > 12) {
+              if ((uint32_t)w0 > SV_INLINE_MAX) {
                 if (w1 >> 32) atomicOr((unsigned long long*)&ctrl[3], 8ULL);   // a view's offset is 32 bits
                 v[0] = (uint32_t)w0; v[1] = (uint32_t)(w0 >> 32); v[2] = 0; v[3] = (uint32_t)w1;
               } else {
@@ -784,7 +784,7 @@ __global__ __launch_bounds__(256) void gb_result_kernel(GbLayout L, const uint64
             // -> 16-byte view: {len, bytes[12]} inline, or {len, prefix, buffer 0, offset into the table's arena} (dbhip_groupby_arena)
             uint32_t* v = (uint32_t*)o + 4 * i;
             const uint32_t len = s[1] ? (uint32_t)s[0] : 0;
-            if (len > 12) {
+            if (len > SV_INLINE_MAX) {
               const uint64_t off = s[2] - (uint64_t)P.arena;
               if (off >> 32) atomicOr((unsigned long long*)&ctrl[3], 8ULL);   // a view's offset is 32 bits
               v[0] = len; v[1] = (uint32_t)(s[0] >> 32); v[2] = 0; v[3] = (uint32_t)off;
@@ -939,7 +939,7 @@ __global__ __launch_bounds__(256) void gb_state_fields_kernel(GbLayout L, const 
               // the value column of the Nullable(String) state: a 16-byte view, long strings by offset into the table's arena (buffer 0)
               uint32_t* v = (uint32_t*)P.f[f] + 4 * i;
               const uint32_t len = s[1] ? (uint32_t)s[0] : 0;
-              if (len > 12) {
+              if (len > SV_INLINE_MAX) {
                 const uint64_t off = s[2] - (uint64_t)arena;
                 if (off >> 32) atomicOr((unsigned long long*)&ctrl[3], 8ULL);
                 v[0] = len; v[1] = (uint32_t)(s[0] >> 32); v[2] = 0; v[3] = (uint32_t)off;
@@ -1019,8 +1019,8 @@ __global__ __launch_bounds__(256) void gb_states_from_fields_kernel(GbLayout L, 
             const uint32_t len = v[0];
             uint64_t ww[2] = {0, 0};
             if (has) {
-              if (len <= 12) { bool vv; gb_load_words(vc, i, ww, &vv); }
-              else if (vc.buffers) { ww[0] = ((uint64_t)v[1] << 32) | len; ww[1] = (uint64_t)((const uint8_t*)vc.buffers[v[2]] + v[3]); }
+              if (sv_is_inline(len)) { bool vv; gb_load_words(vc, i, ww, &vv); }
+              else if (vc.buffers) { ww[0] = ((uint64_t)v[1] << 32) | len; ww[1] = (uint64_t)sv_bytes(v, vc.buffers); }
               else { has = false; atomicOr((unsigned long long*)&ctrl[3], 2ULL); }   // a long view without data buffers: the merge reports it
             }
             s[0] = has ? ww[0] : 0; s[2] = has ? ww[1] : 0;

@@ -7,6 +7,7 @@
 //   FilterExecutor::select -> ascending u32 row ids      filter/filter_executor.rs:81-118
 //   DataBlock::take                                      kernels/take.rs:43
 #include "dev_common.h"
+#include "dev_strview.h"
 #include "dev_load.h"
 #include "runtime.h"
 
@@ -39,27 +40,18 @@ __device__ __forceinline__ bool apply_cmp(int op, int c) {
   }
 }
 
-struct View {
-  uint32_t len, w1, w2, w3;  // binview/view.rs:30-42: inline bytes in w1..w3 when len<=12,
-};                            // else w1=prefix, w2=buffer_idx, w3=offset
-
-__device__ __forceinline__ const uint8_t* view_ptr(const View& v, const View* self,
-                                                   const void* const* buffers) {
-  if (v.len <= 12) return (const uint8_t*)self + 4;
-  return (const uint8_t*)buffers[v.w2] + v.w3;
-}
-
-__device__ int cmp3_views(const View* a, const void* const* abuf, const View* b,
-                          const void* const* bbuf) {
-  View va = *a, vb = *b;
-  const uint8_t* pa = view_ptr(va, a, abuf);
-  const uint8_t* pb = view_ptr(vb, b, bbuf);
-  uint32_t m = va.len < vb.len ? va.len : vb.len;
+// a, b: two 16-byte views where they lie (dev_strview.h)
+__device__ int cmp3_views(const uint4* a, const void* const* abuf, const uint4* b, const void* const* bbuf) {
+  const uint4 va = *a, vb = *b;   // index and offset are loaded with the length, not behind it
+  const uint32_t la = va.x, lb = vb.x;
+  const uint8_t* pa = sv_bytes(a, la, va.z, va.w, abuf);
+  const uint8_t* pb = sv_bytes(b, lb, vb.z, vb.w, bbuf);
+  uint32_t m = la < lb ? la : lb;
   for (uint32_t i = 0; i < m; ++i) {
     int d = (int)pa[i] - (int)pb[i];
     if (d) return d < 0 ? -1 : 1;
   }
-  return (va.len > vb.len) - (va.len < vb.len);
+  return (la > lb) - (la < lb);
 }
 
 struct CmpParams {
@@ -167,12 +159,11 @@ __global__ __launch_bounds__(256) void cmp_kernel(CmpParams p) {
           }
         }
       } else if (p.type == DBHIP_T_STRING) {
-        const View* a = (const View*)p.a;
-        const View* b = (const View*)p.b;
+        const uint4* a = (const uint4*)p.a;
+        const uint4* b = (const uint4*)p.b;
         for (int k = 0; k < 4; ++k) {
           if (i0 + k < p.n) {
-            int c = cmp3_views(a + (p.a_scalar ? 0 : i0 + k), p.abuf, b + (p.b_scalar ? 0 : i0 + k),
-                               p.bbuf);
+            int c = cmp3_views(a + (p.a_scalar ? 0 : i0 + k), p.abuf, b + (p.b_scalar ? 0 : i0 + k), p.bbuf);
             nib |= (uint32_t)apply_cmp(p.op, c) << k;
           }
         }

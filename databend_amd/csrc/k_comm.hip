@@ -13,6 +13,7 @@
 // links carry traffic at once; blocks are fixed-size so the collective needs no size negotiation.
 #include "runtime.h"
 #include "dev_scan.h"
+#include "dev_strview.h"
 
 #include <dlfcn.h>
 #include <string.h>
@@ -316,7 +317,7 @@ __global__ __launch_bounds__(256) void topk_regroup_kernel(const T* __restrict__
 __global__ __launch_bounds__(256) void xs_long_len_kernel(const uint32_t* __restrict__ views, int64_t n, uint32_t* __restrict__ out) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const uint32_t len = views[4 * i];
-    out[i] = len > 12 ? len : 0u;
+    out[i] = sv_is_inline(len) ? 0u : len;
   }
 }
 // the long strings of the scattered rows, copied back to back in row order into `packed` (off[i] = where row i's bytes go), and the view
@@ -331,7 +332,7 @@ __global__ __launch_bounds__(256) void xs_pack_kernel(uint32_t* __restrict__ vie
     uint32_t len = 0, bufi = 0, boff = 0;
     uint64_t o = 0;
     if (i < n) { len = views[4 * i]; bufi = views[4 * i + 2]; boff = views[4 * i + 3]; o = off[i]; }
-    const bool lng = len > 12;
+    const bool lng = !sv_is_inline(len);
     // the destination whose piece row i belongs to: the last d with dest_start[d] <= i
     uint64_t piece0 = 0;
     if (lng) {
@@ -365,7 +366,7 @@ __global__ void xs_pick_kernel(const uint64_t* __restrict__ off, const int64_t* 
 __global__ __launch_bounds__(256) void xs_rebase_kernel(uint32_t* __restrict__ views, int64_t n, const int64_t* __restrict__ row_start,
                                                         const uint64_t* __restrict__ byte_start, int world, uint32_t* __restrict__ err) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    if (views[4 * i] <= 12) continue;
+    if (sv_is_inline(views[4 * i])) continue;
     int lo = 0, hi = world;
     while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (row_start[mid] <= i) lo = mid; else hi = mid; }
     const uint64_t o = (uint64_t)views[4 * i + 3] + byte_start[lo];

@@ -16,6 +16,7 @@
 // either unit definition a segment's end is monotone in its start. An end-anchored last segment is matched backwards from the end.
 #include <string.h>
 #include "dev_common.h"
+#include "dev_strview.h"
 #include "runtime.h"
 #define LIKE_FN __device__ __forceinline__
 #include "like_match.h"
@@ -64,8 +65,9 @@ __global__ __launch_bounds__(256) void like_rows_kernel(const LikeParams P) {
       LaneValue v{vw.x, vw.y, vw.z, vw.w, 0, 1, 0};
       bool usable = true;
       if (!v.is_inline()) {
-        usable = vw.z < (uint32_t)P.n_buffers && P.buffers[vw.z] != nullptr;
-        if (usable) v.base = (uintptr_t)P.buffers[vw.z] + vw.w;
+        const uint8_t* bytes = nullptr;
+        usable = sv_bytes_checked(P.views + i, vw.x, vw.z, vw.w, P.buffers, P.n_buffers, &bytes);   // (false: a long view that points nowhere)
+        if (usable) v.base = (uintptr_t)bytes;
       }
       if (usable) {
         const bool hit = like_lane_decide(v, S, kind, nseg, m, a_start, a_end, unit_byte, &listed);
@@ -97,7 +99,7 @@ __global__ __launch_bounds__(256) void like_long_kernel(const LikeParams P) {
   for (uint32_t k = blockIdx.x * 4 + (threadIdx.x >> 6); k < count; k += nwaves) {
     const uint32_t row = P.long_rows[k];
     const uint4 vw = P.views[row];
-    WaveValue v{vw.x, (const uint8_t*)P.buffers[vw.z] + vw.w};
+    WaveValue v{vw.x, (const uint8_t*)P.buffers[vw.z] + vw.w};   // (a long view that pass 1 has checked: dev_strview.h sv_bytes_checked)
     // the anchored segments: every lane does the same work on the same bytes
     uint32_t pos = 0, tail = v.len, first = 0, last = nseg;
     bool ok = true, done = false;

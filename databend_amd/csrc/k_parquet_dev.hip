@@ -881,19 +881,9 @@ struct DvXJob {
 
 // 16-byte view of the `len` bytes at p, which lie at offset `off` of buffer `buf` of the column (store_view for a length known apart)
 __device__ __forceinline__ void dv_view(const uint8_t* __restrict__ p, uint32_t len, uint32_t buf, uint32_t off, void* __restrict__ out, uint64_t o) {
-  uint32_t w1 = 0, w2 = 0, w3 = 0;
-  if (len <= 12) {
-#pragma unroll
-    for (uint32_t b = 0; b < 12; ++b) {
-      const uint32_t x = b < len ? (uint32_t)p[b] << (8 * (b & 3)) : 0u;
-      if (b < 4) w1 |= x; else if (b < 8) w2 |= x; else w3 |= x;
-    }
-  } else {
-    w1 = (uint32_t)load_le(p, 4);
-    w2 = buf;
-    w3 = off;
-  }
-  ((uint4*)out)[o] = make_uint4(len, w1, w2, w3);
+  uint32_t w[4];
+  sv_make(p, len, buf, off, w);
+  ((uint4*)out)[o] = make_uint4(w[0], w[1], w[2], w[3]);
 }
 
 // exclusive prefix sum of v over the workgroup (256 threads); *tot: the workgroup's sum. Called by all threads.

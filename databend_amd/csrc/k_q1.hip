@@ -72,18 +72,6 @@ struct KeyTable {
   uint64_t key[MAX_SLOTS][4];
 };
 
-// canonical words of an inline view (bytes past len zeroed), false if len > 12
-__device__ __forceinline__ bool view_words(U4 v, uint64_t w[2]) {
-  uint32_t len = v.x;
-  uint32_t d1 = v.y, d2 = v.z, d3 = v.w;
-  uint32_t m1 = len >= 4 ? 0xffffffffu : (len == 0 ? 0u : (0xffffffffu >> (8 * (4 - len))));
-  uint32_t m2 = len >= 8 ? 0xffffffffu : (len <= 4 ? 0u : (0xffffffffu >> (8 * (8 - len))));
-  uint32_t m3 = len >= 12 ? 0xffffffffu : (len <= 8 ? 0u : (0xffffffffu >> (8 * (12 - len))));
-  w[0] = ((uint64_t)(d1 & m1) << 32) | len;
-  w[1] = ((uint64_t)(d3 & m3) << 32) | (d2 & m2);
-  return len <= 12;
-}
-
 __device__ __forceinline__ uint64_t hash_view_words(const uint64_t w[2]) {
   return agg_hash_inline_view((uint32_t)w[0], (uint32_t)(w[0] >> 32), (uint32_t)w[1], (uint32_t)(w[1] >> 32));
 }
@@ -144,7 +132,7 @@ template <int SLOTS>
 __device__ __forceinline__ int resolve_slot(KeyTable* T, TabCache<SLOTS>& C, bool row_valid, U4 v0, U4 v1,
                                             uint32_t& flags) {
   uint64_t ka[2], kb[2];
-  bool ok = view_words(v0, ka) & view_words(v1, kb);
+  bool ok = sv_key_words(v0.x, v0.y, v0.z, v0.w, ka[0], ka[1]) & sv_key_words(v1.x, v1.y, v1.z, v1.w, kb[0], kb[1]);   // false: a long view
   flags |= (row_valid & !ok) ? 2u : 0u;
   const bool want = row_valid & ok;
   int slot = C.lookup(ka[0], ka[1], kb[0], kb[1]);

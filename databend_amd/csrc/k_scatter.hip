@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "dev_common.h"
+#include "dev_strview.h"
 #include "runtime.h"
 
 using namespace dbhip;
@@ -78,7 +79,7 @@ __device__ __forceinline__ uint64_t sip_value(const SipCol& c, int64_t row) {
     case DBHIP_T_STRING: {
       const uint32_t* v = (const uint32_t*)c.data + 4 * j;
       const uint32_t len = v[0];
-      const uint8_t* p = len <= 12 ? (const uint8_t*)(v + 1) : (const uint8_t*)c.buffers[v[2]] + v[3];
+      const uint8_t* p = sv_bytes(v, c.buffers);
       uint32_t at = 0;
       for (; at + 8 <= len; at += 8) {
         uint64_t m = 0;
@@ -155,7 +156,7 @@ int32_t make_sip_col(const dbhip_col& c, int64_t n, hipStream_t s, const char* f
     uint32_t mx = 0;
     DBHIP_CHECK(hipMemcpyAsync(&mx, flag, 4, hipMemcpyDeviceToHost, s));
     DBHIP_CHECK(hipStreamSynchronize(s));
-    if (mx > 12) { set_error("%s: string key %d holds values longer than 12 bytes but no data buffers", fn, k); return DBHIP_ERR_INVALID; }
+    if (mx > SV_INLINE_MAX) { set_error("%s: string key %d holds values longer than 12 bytes but no data buffers", fn, k); return DBHIP_ERR_INVALID; }
   }
   const bool ok = (t >= DBHIP_T_BOOL && t <= DBHIP_T_STRING) || t == DBHIP_T_DEC256;
   if (!ok) { set_error("%s: key %d has unsupported type %d", fn, k, t); return DBHIP_ERR_UNSUPPORTED; }
@@ -258,13 +259,13 @@ __global__ __launch_bounds__(256) void sc_concat_bits_kernel(ConcatBits A, uint6
 }
 
 // views of one block with the buffer index of long values rebased (the concatenated column's buffer table is the blocks' tables
-// back to back); inline values (<= 12 bytes) are copied as they are
+// back to back); inline values are copied as they are
 __global__ __launch_bounds__(256) void sc_rebase_views_kernel(const uint32_t* __restrict__ src, int64_t n, uint32_t buffer_base, int is_scalar,
                                                               uint32_t* __restrict__ out) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const uint4 v = ((const uint4*)src)[is_scalar ? 0 : i];
     uint4 o = v;
-    if (v.x > 12) o.z = v.z + buffer_base;
+    sv_rebase(v.x, o.z, o.w, buffer_base, 0u);
     ((uint4*)out)[i] = o;
   }
 }

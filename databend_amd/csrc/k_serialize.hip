@@ -13,6 +13,7 @@
 // is the KeysU128 key of the existing machinery (k_join.hip), and every emitted pair is then VERIFIED byte for byte against the
 // build side's rows, which the table keeps — equal bytes are what the reference's table compares, the hash only routes.
 #include "dev_common.h"
+#include "dev_strview.h"
 #include "dev_scan.h"
 #include "runtime.h"
 
@@ -37,13 +38,6 @@ struct SerArgs {
   int32_t ncols;
   int64_t n;
 };
-
-__device__ __forceinline__ const uint8_t* view_bytes(const SerCol& c, int64_t j, uint32_t* len) {
-  const uint32_t* v = (const uint32_t*)c.data + 4 * j;
-  *len = v[0];
-  if (*len <= 12) return (const uint8_t*)(v + 1);
-  return (const uint8_t*)c.buffers[v[2]] + v[3];
-}
 
 __global__ __launch_bounds__(256) void ser_size_kernel(SerArgs A, uint32_t* sizes, uint8_t* all_valid) {
   const int64_t n_pad = (A.n + 63) & ~63LL;
@@ -85,8 +79,9 @@ __global__ __launch_bounds__(256) void ser_write_kernel(SerArgs A, const uint64_
         for (int b = 0; b < C.fixed; ++b) p[b] = s[b];
         p += C.fixed;
       } else {
-        uint32_t len;
-        const uint8_t* s = view_bytes(C, j, &len);
+        const uint32_t* v = (const uint32_t*)C.data + 4 * j;
+        const uint32_t len = v[0];
+        const uint8_t* s = sv_bytes(v, C.buffers);
         const uint64_t l64 = len;
         for (int b = 0; b < 8; ++b) p[b] = (uint8_t)(l64 >> (8 * b));
         p += 8;

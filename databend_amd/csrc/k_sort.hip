@@ -17,6 +17,7 @@
 // row-id order (stable), which is one of the orders the reference may produce.
 #include <string.h>
 #include "dev_common.h"
+#include "dev_strview.h"
 #include "dev_scan.h"
 #include "runtime.h"
 
@@ -79,7 +80,7 @@ __device__ __forceinline__ uint64_t sort_encode(const SortCol& c, uint32_t row, 
         if (part == 0) return len;
         const uint32_t at = 8u * (uint32_t)(c.nparts - 1 - part);
         if (at >= len) return 0;
-        const uint8_t* p = len <= 12 ? (const uint8_t*)(v + 1) : (const uint8_t*)c.buffers[v[2]] + v[3];
+        const uint8_t* p = sv_bytes(v, c.buffers);
         const uint32_t take = len - at < 8 ? len - at : 8;
         uint64_t img = 0;
         for (uint32_t b = 0; b < take; ++b) img |= (uint64_t)p[at + b] << (8 * (7 - b));
@@ -92,7 +93,9 @@ __device__ __forceinline__ uint64_t sort_encode(const SortCol& c, uint32_t row, 
       const uint32_t* v = (const uint32_t*)c.data + 4 * (uint64_t)row;
       const uint32_t len = v[0];
       uint32_t d1 = v[1], d2 = v[2], d3 = v[3];
-      const uint32_t l = len > 12 ? 4 : len;  // long strings: only the 4-byte prefix is inline (flagged by the caller)
+      const uint32_t l = sv_is_inline(len) ? len : 4;  // long strings: only the 4-byte prefix is inline (flagged by the caller)
+      // (the branching form of dev_strview.h's sv_canon mask, kept here: the select form made this sort measurably slower,
+      // profiles/strview_ab.json)
       if (l < 4) { d1 &= (l == 0) ? 0u : (0xffffffffu >> (8 * (4 - l))); d2 = 0; d3 = 0; }
       else if (l < 8) { d2 &= (l == 4) ? 0u : (0xffffffffu >> (8 * (8 - l))); d3 = 0; }
       else if (l < 12) { d3 &= (l == 8) ? 0u : (0xffffffffu >> (8 * (12 - l))); }
@@ -729,7 +732,7 @@ int32_t dbhip_sort_bound_partition(const dbhip_col* keys, const dbhip_col* bound
       uint32_t mx = 0;
       DBHIP_CHECK(hipMemcpyAsync(&mx, flag, 4, hipMemcpyDeviceToHost, s));
       DBHIP_CHECK(hipStreamSynchronize(s));
-      if (mx > 12) {
+      if (mx > SV_INLINE_MAX) {
         if (!keys[k].buffers || (nbounds && !bounds[k].buffers)) {
           set_error("dbhip_sort_bound_partition: string key %d holds values longer than 12 bytes but the rows or the bounds carry no data buffers", k);
           return DBHIP_ERR_INVALID;
@@ -863,7 +866,7 @@ int32_t dbhip_sort_perm(const dbhip_col* keys, const uint8_t* desc_host, const u
     uint32_t mx = 0;
     DBHIP_CHECK(hipMemcpyAsync(&mx, long_flag, 4, hipMemcpyDeviceToHost, s));
     DBHIP_CHECK(hipStreamSynchronize(s));
-    if (mx > 12) {
+    if (mx > SV_INLINE_MAX) {
       if (!keys[k].buffers) { set_error("dbhip_sort_perm: string key %d holds values longer than 12 bytes but no data buffers", k); return DBHIP_ERR_INVALID; }
       if (mx > 4096) { set_error("dbhip_sort_perm: string key %d holds a %u-byte value (> 4096: keep the CPU operator for this block)", k, mx); return DBHIP_ERR_UNSUPPORTED; }
       str_parts[k] = 1 + (int)((mx + 7) / 8);

@@ -16,6 +16,7 @@
 #include <string.h>
 #include <type_traits>
 #include "dev_common.h"
+#include "dev_strview.h"
 #include "runtime.h"
 
 using namespace dbhip;
@@ -75,7 +76,7 @@ __device__ __forceinline__ bool win_key_equal(const WinKey& c, uint32_t a, uint3
       const uint32_t* vb = (const uint32_t*)c.data + 4 * (uint64_t)b;
       const uint32_t len = va[0];
       if (len != vb[0]) return false;
-      if (len <= 12) {
+      if (sv_is_inline(len)) {
         const uint8_t* pa = (const uint8_t*)(va + 1);
         const uint8_t* pb = (const uint8_t*)(vb + 1);
         for (uint32_t k = 0; k < len; ++k)
@@ -84,8 +85,8 @@ __device__ __forceinline__ bool win_key_equal(const WinKey& c, uint32_t a, uint3
       }
       if (va[1] != vb[1]) return false;      // the 4-byte prefix
       if (!c.buffers || va[2] >= (uint32_t)c.n_buffers || vb[2] >= (uint32_t)c.n_buffers) { *bad = 1; return false; }   // no table, or a view that points past it
-      const uint8_t* pa = (const uint8_t*)c.buffers[va[2]] + va[3];
-      const uint8_t* pb = (const uint8_t*)c.buffers[vb[2]] + vb[3];
+      const uint8_t* pa = sv_bytes(va, c.buffers);
+      const uint8_t* pb = sv_bytes(vb, c.buffers);
       if (pa == pb) return true;
       uint32_t k = 4;
       if ((((uintptr_t)pa | (uintptr_t)pb) & 7) == 0) {   // both values begin on an 8-byte boundary: whole words, then the tail

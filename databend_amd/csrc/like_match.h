@@ -4,6 +4,7 @@
 #pragma once
 #include <stdint.h>
 #include <string.h>
+#include "dev_strview.h"
 
 #ifndef LIKE_LOAD_U32
 #define LIKE_LOAD_U32(addr, value) (*(const uint32_t*)(addr))
@@ -87,7 +88,7 @@ struct LaneValue {
   uintptr_t base;
   uintptr_t cached_at;
   uint32_t cached;
-  LIKE_FN bool is_inline() const { return len <= 12; }
+  LIKE_FN bool is_inline() const { return sv_is_inline(len); }
   LIKE_FN uint32_t load(uintptr_t a) const { return LIKE_LOAD_U32(a, *this); }   // a is a multiple of 4 and the word holds a byte of the value
   // four value bytes from position `pos` of an inline value (bytes past the view's 12 read as 0)
   LIKE_FN uint32_t inline_word(uint32_t pos) const {

@@ -4,6 +4,7 @@
 #pragma once
 #include "dev_common.h"
 #include "dev_scan.h"
+#include "dev_strview.h"
 #include "runtime.h"
 
 #include <string.h>
@@ -318,15 +319,8 @@ __device__ __forceinline__ void store_plain(const PqConv& cv, const uint8_t* p, 
 // 16-byte view of the string whose bytes start at chunk offset `off` (its 4-byte length prefix sits right before)
 __device__ __forceinline__ void store_view(const uint8_t* chunk, uint32_t off, void* out, uint64_t o) {
   const uint8_t* p = chunk + off;
-  const uint32_t len = (uint32_t)load_le(p - 4, 4);
-  uint32_t w[4] = {len, 0, 0, 0};
-  if (len <= 12) {
-    for (uint32_t b = 0; b < len; ++b) w[1 + (b >> 2)] |= (uint32_t)p[b] << (8 * (b & 3));
-  } else {
-    w[1] = (uint32_t)load_le(p, 4);
-    w[2] = 0;     // buffer index: the chunk itself is buffer 0 of the column
-    w[3] = off;
-  }
+  uint32_t w[4];
+  sv_make(p, (uint32_t)load_le(p - 4, 4), 0u, off, w);   // buffer index: the chunk itself is buffer 0 of the column
   ((uint4*)out)[o] = make_uint4(w[0], w[1], w[2], w[3]);
 }
 

@@ -585,3 +585,25 @@ def test_min_max_over_decimal128(gpu, oracle, n, card):
     add(g2, half, n)
     g1.merge_serialized(g2.flush_serialized())
     assert norm(g1.result()) == norm(exp)
+
+
+# ---- String keys: the bytes past an inline value, and long values in a second buffer (tests/strview_cases.py) ------------------------
+@pytest.mark.parametrize("inline_only", [False, True], ids=["with_long", "inline_only"])
+def test_string_keys_ignore_the_bytes_past_an_inline_value(gpu, oracle, inline_only):
+    """group_hash and a GroupBy over the shared String column, built with clean and with 0xFF padding: the same hashes as the oracle,
+    the same groups and counts as a Counter over the strings, the keys read back equal. inline_only takes the canonical-word path
+    (no key longer than 12 bytes), the other one the general path."""
+    import collections
+    from tests import strview_cases as S
+    p = S.build(gpu, S.values(inline_only))
+    exp = np.zeros(S.N, np.uint64)
+    assert oracle.orc_group_hash(O.cols([p.host]), 1, C.c_int64(S.N), exp.ctypes.data_as(C.c_void_p)) == 0
+    want = sorted(collections.Counter(p.vals).items())
+    assert 1 < len(want) < S.N
+    for name, col in p.both():
+        assert np.array_equal(gpu.group_hash([col], S.N), exp), name
+        g = gpu.GroupBy([T.T_STRING], [(T.AGG_COUNT, 0, 0, 0, 0)])
+        g.add_block([col], [None], S.N)
+        got = sorted(g.result())
+        g.destroy()
+        assert got == want, name

@@ -447,3 +447,17 @@ def test_200000_rows(gpu, pattern):
     assert_rows(run_like(gpu, case["col"], pattern), exp, case["values"], f"pattern {pattern!r}")
     nexp = expect(case["values"], case["valid"], pattern, negate=True, cache="big")
     assert_rows(run_like(gpu, case["col"], pattern, negate=True), nexp, case["values"], f"NOT pattern {pattern!r}")
+
+
+# ---- the bytes past an inline value, and long values in a second buffer (tests/strview_cases.py) --------------------------------------
+def test_like_ignores_the_bytes_past_an_inline_value(gpu):
+    """the shared String column with clean and with 0xFF padding against a PREFIX and a SEGMENTS pattern (and one that asks for the
+    padding byte itself): the reference's bits both times"""
+    from tests import strview_cases as S
+    p = S.build(gpu)
+    for pattern in (b"ab%", b"%a%b%a", b"%\xff", b"a\xff%"):
+        exp = expect(p.vals, None, pattern)
+        assert True in exp and False in exp, pattern
+        for name, col in p.both():
+            assert_rows(run_like(gpu, col, pattern), exp, p.vals, f"{name} {pattern!r}")
+    assert R.kind_of(b"ab%", BS) == R.PREFIX and R.kind_of(b"%a%b%a", BS) == R.SEGMENTS

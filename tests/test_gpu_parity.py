@@ -961,3 +961,18 @@ def _strip(e):
     if e[0] in ("cmp", "bool"):
         return e[:-1]
     return (e[0], [_strip(c) for c in e[1]])
+
+
+# ---- String compares: the bytes past an inline value, and long values in a second buffer (tests/strview_cases.py) ---------------------
+def test_string_cmp_ignores_the_bytes_past_an_inline_value(gpu):
+    """EQ and LT, column against column, over the shared String column and the same column 14 rows on (the same lengths, another stem),
+    with clean and with 0xFF padding: Python's bytes order both times"""
+    from tests import strview_cases as S
+    a = S.build(gpu)
+    b = S.build(gpu, a.vals[14:] + a.vals[:14])
+    for op, holds in ((T.CMP_EQ, lambda x, y: x == y), (T.CMP_LT, lambda x, y: x < y)):
+        exp = [holds(x, y) for x, y in zip(a.vals, b.vals)]
+        assert True in exp and False in exp
+        for (name, ca), (_, cb) in zip(a.both(), b.both()):
+            assert gpu.cmp(op, ca, cb, S.N).to_numpy().tolist() == exp, (name, op)
+        assert gpu.cmp(op, a.clean, b.dirty, S.N).to_numpy().tolist() == exp, op

@@ -440,3 +440,21 @@ def test_stream_cancel_stops_multi_launch_operators(gpu):
     T.check(L.dbhip_stream_cancel(s))
     T.check(L.dbhip_stream_destroy(s))          # destroying the stream clears the mark
     g.destroy(); g2.destroy()
+
+
+# ---- the bytes past an inline value, long values in a second buffer, and the rebase of a concat (tests/strview_cases.py) --------------
+def test_string_hash_and_concat_ignore_the_bytes_past_an_inline_value(gpu):
+    """siphash64 over the shared String column with clean and with 0xFF padding equals the oracle both times; the concat of the two
+    blocks (whose views are rebased onto a table of four buffers) reads back the strings twice"""
+    from tests import strview_cases as S
+    p = S.build(gpu)
+    exp = orc_hash(p.host, S.N)
+    for name, col in p.both():
+        assert np.array_equal(gpu.siphash64(col), exp), name
+    both = gpu.concat_columns([p.clean, p.dirty])
+    assert both.n == 2 * S.N and both.n_buffers == 4
+    assert both.string_values() == p.vals + p.vals
+    views = both.to_numpy().view(np.uint32).reshape(-1, 4)
+    long_rows = np.array([len(v) > 12 for v in p.vals])
+    assert set(views[:S.N][long_rows, 2].tolist()) == {0, 1} and set(views[S.N:][long_rows, 2].tolist()) == {2, 3}
+    assert np.array_equal(views[S.N:][~long_rows], p.dirty.to_numpy().view(np.uint32).reshape(-1, 4)[~long_rows])   # inline views: bit-identical

@@ -321,3 +321,16 @@ def test_bound_partition_of_sliced_nullable_keys(gpu, nb):
         bounds = [c.take(R.sort_perm_fast(raw, desc, nf)) for c in raw]
         check_partition(gpu, rows, grows, bounds, desc, nf, "sliced rows")
         check_partition(gpu, rows[:1], grows[:1], bounds[:1], desc[:1], nf[:1], "one sliced key")
+
+
+# ---- the bytes past an inline value, and long values in a second buffer (tests/strview_cases.py) --------------------------------------
+@pytest.mark.parametrize("inline_only", [False, True], ids=["with_long", "inline_only"])
+def test_string_sort_ignores_the_bytes_past_an_inline_value(gpu, inline_only):
+    """the shared String column with clean and with 0xFF padding: the reference's permutation both times. inline_only sorts by the two
+    images of the inline view (no value longer than 12 bytes), the other column by the images of the bytes where they live."""
+    from tests import strview_cases as S
+    p = S.build(gpu, S.values(inline_only))
+    for desc in (0, 1):
+        exp = R.sort_perm([R.KeyCol("lstr", p.vals)], [desc], [0])
+        for name, col in p.both():
+            assert np.array_equal(gpu.sort_perm([col], desc=[desc]), exp), (name, desc)

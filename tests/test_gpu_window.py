@@ -470,3 +470,20 @@ def test_sort_then_window_against_sqlite(gpu):
     assert rank.tolist() == e_rank
     assert nullable_list(run, run_valid) == e_run
     assert nullable_list(lag, lag_valid) == e_lag
+
+
+# ---- the bytes past an inline value, and long values in a second buffer (tests/strview_cases.py) --------------------------------------
+def test_string_keys_ignore_the_bytes_past_an_inline_value(gpu):
+    """the shared String column, sorted, as partition key and as order key, with clean and with 0xFF padding: the reference's four
+    arrays both times (equal long values lie in different buffers)"""
+    from tests import strview_cases as S
+    vals = sorted(S.values())
+    p = S.build(gpu, vals)
+    half = [v[:len(v) // 2] for v in vals]             # a coarser partition key: partitions of several peer groups
+    q = S.build(gpu, half)
+    exp = W.boundaries([R.KeyCol("lstr", half)], [R.KeyCol("lstr", vals)], S.N)
+    assert len(set(exp[0])) > 1 and len(set(exp[2])) > len(set(exp[0])) and len(set(exp[2])) < S.N
+    for (name, part), (_, order) in zip(q.both(), p.both()):
+        got = gpu.Window([part], [order]).bounds()
+        for g, e in zip(got, exp):
+            assert g.tolist() == list(e), name

@@ -160,3 +160,17 @@ def rows_strings(hcol):
             o = int.from_bytes(v[12:16].tobytes(), "little")
             out.append(buf[o:o + ln].tobytes())
     return out
+
+
+@pytest.mark.gpu
+def test_device_serialization_ignores_the_bytes_past_an_inline_value(gpu):
+    """the shared String column (tests/strview_cases.py) with clean and with 0xFF padding: the oracle's bytes both times"""
+    from tests import strview_cases as S
+    p = S.build(gpu)
+    off_o, data_o = oracle_serialize([p.host], S.N)
+    assert rows_of(off_o, data_o) == [struct.pack("<Q", len(v)) + v for v in p.vals]
+    for name, col in p.both():
+        off, data, _, total = gpu.serialize_keys([col], S.N)
+        assert total == len(data_o), name
+        assert np.array_equal(off.to_numpy(np.uint64, S.N + 1), off_o), name
+        assert np.array_equal(data.to_numpy(np.uint8, total), data_o), name
