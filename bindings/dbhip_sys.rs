@@ -62,6 +62,8 @@ pub const DBHIP_EX_NOT: i32 = 14;   // dbhip_expr_op
 pub const DBHIP_EX_CAST: i32 = 15;   // dbhip_expr_op
 pub const DBHIP_EX_IF: i32 = 16;   // dbhip_expr_op
 pub const DBHIP_EX_IS_TRUE: i32 = 17;   // dbhip_expr_op
+pub const DBHIP_EX_DT_PART: i32 = 18;   // dbhip_expr_op
+pub const DBHIP_EX_DT_TRUNC: i32 = 19;   // dbhip_expr_op
 pub const DBHIP_AGG_COUNT: i32 = 0;   // dbhip_agg_kind
 pub const DBHIP_AGG_SUM: i32 = 1;   // dbhip_agg_kind
 pub const DBHIP_AGG_MIN: i32 = 2;   // dbhip_agg_kind
@@ -89,6 +91,34 @@ pub const DBHIP_LIKE_CONTAINS: i32 = 3;   // dbhip_like_kind_t
 pub const DBHIP_LIKE_SEGMENTS: i32 = 4;   // dbhip_like_kind_t
 pub const DBHIP_LIKE_NEGATE: i32 = 1;
 pub const DBHIP_LIKE_UNIT_BYTE: i32 = 2;
+pub const DBHIP_DT_PART_YEAR: i32 = 0;   // dbhip_dt_part_t
+pub const DBHIP_DT_PART_QUARTER: i32 = 1;   // dbhip_dt_part_t
+pub const DBHIP_DT_PART_MONTH: i32 = 2;   // dbhip_dt_part_t
+pub const DBHIP_DT_PART_DAY: i32 = 3;   // dbhip_dt_part_t
+pub const DBHIP_DT_PART_DAY_OF_YEAR: i32 = 4;   // dbhip_dt_part_t
+pub const DBHIP_DT_PART_DOW_ISO: i32 = 5;   // dbhip_dt_part_t
+pub const DBHIP_DT_PART_DOW_SUNDAY0: i32 = 6;   // dbhip_dt_part_t
+pub const DBHIP_DT_PART_ISO_YEAR: i32 = 7;   // dbhip_dt_part_t
+pub const DBHIP_DT_PART_ISO_WEEK: i32 = 8;   // dbhip_dt_part_t
+pub const DBHIP_DT_PART_HOUR: i32 = 9;   // dbhip_dt_part_t
+pub const DBHIP_DT_PART_MINUTE: i32 = 10;   // dbhip_dt_part_t
+pub const DBHIP_DT_PART_SECOND: i32 = 11;   // dbhip_dt_part_t
+pub const DBHIP_DT_PART_MICROSECOND: i32 = 12;   // dbhip_dt_part_t
+pub const DBHIP_DT_PART_EPOCH_SECOND: i32 = 13;   // dbhip_dt_part_t
+pub const DBHIP_DT_PART_YYYYMM: i32 = 14;   // dbhip_dt_part_t
+pub const DBHIP_DT_PART_YYYYMMDD: i32 = 15;   // dbhip_dt_part_t
+pub const DBHIP_DT_PART_YYYYMMDDHH: i32 = 16;   // dbhip_dt_part_t
+pub const DBHIP_DT_PART_YYYYMMDDHHMMSS: i32 = 17;   // dbhip_dt_part_t
+pub const DBHIP_DT_PART_DATE: i32 = 18;   // dbhip_dt_part_t
+pub const DBHIP_DT_UNIT_YEAR: i32 = 0;   // dbhip_dt_unit_t
+pub const DBHIP_DT_UNIT_QUARTER: i32 = 1;   // dbhip_dt_unit_t
+pub const DBHIP_DT_UNIT_MONTH: i32 = 2;   // dbhip_dt_unit_t
+pub const DBHIP_DT_UNIT_WEEK: i32 = 3;   // dbhip_dt_unit_t
+pub const DBHIP_DT_UNIT_DAY: i32 = 4;   // dbhip_dt_unit_t
+pub const DBHIP_DT_UNIT_HOUR: i32 = 5;   // dbhip_dt_unit_t
+pub const DBHIP_DT_UNIT_MINUTE: i32 = 6;   // dbhip_dt_unit_t
+pub const DBHIP_DT_UNIT_SECOND: i32 = 7;   // dbhip_dt_unit_t
+pub const DBHIP_DT_WEEK_SUNDAY: i32 = 1;
 pub const DBHIP_VEC_COSINE: i32 = 0;   // dbhip_vec_metric
 pub const DBHIP_VEC_L2: i32 = 1;   // dbhip_vec_metric
 pub const DBHIP_VEC_DOT: i32 = 2;   // dbhip_vec_metric
@@ -184,6 +214,15 @@ pub struct dbhip_window_frame {
     pub _pad: i32,
     pub start_offset: i64,
     pub end_offset: i64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct dbhip_tz {
+    pub offset_s: i32,
+    pub n_transitions: i32,
+    pub at_utc_s: *const i64,
+    pub offset_after_s: *const i32,
 }
 
 #[repr(C)]
@@ -328,6 +367,11 @@ extern "C" {
     pub fn dbhip_like_kind(pattern_host: *const u8, pattern_len: i32, escape: i32) -> i32;
     pub fn dbhip_like(col: *const dbhip_col, pattern_host: *const u8, pattern_len: i32, escape: i32, flags: i32, n: i64, out_bitmap: *mut u8, stream: *mut c_void) -> i32;
     pub fn dbhip_str_match(kind: i32, col: *const dbhip_col, needle_host: *const u8, needle_len: i32, flags: i32, n: i64, out_bitmap: *mut u8, stream: *mut c_void) -> i32;
+    pub fn dbhip_dt_part_type(part: i32, src_type: i32) -> i32;
+    pub fn dbhip_dt_part(part: i32, src: *const dbhip_col, tz: *const dbhip_tz, n: i64, out: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn dbhip_dt_trunc(unit: i32, flags: i32, src: *const dbhip_col, out_type: i32, tz: *const dbhip_tz, n: i64, out: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn dbhip_dt_add(unit: i32, src: *const dbhip_col, delta: *const dbhip_col, tz: *const dbhip_tz, n: i64, out: *mut c_void, err_bitmap: *mut u8, err_count_dev: *mut u64, stream: *mut c_void) -> i32;
+    pub fn dbhip_dt_diff(unit: i32, a: *const dbhip_col, b: *const dbhip_col, tz: *const dbhip_tz, n: i64, out: *mut i64, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_distance_rows(metric: i32, elem_type: i32, lhs: *const c_void, lhs_is_scalar: i32, rhs: *const c_void, rhs_is_scalar: i32, n: i64, dim: i32, out: *mut c_void, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_distance(metric: i32, base: *const f32, n: i64, dim: i32, queries: *const f32, nq: i32, out: *mut f32, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_topk(metric: i32, base: *const f32, n: i64, dim: i32, queries: *const f32, nq: i32, k: i32, out_idx: *mut u32, out_dist: *mut f32, stream: *mut c_void) -> i32;

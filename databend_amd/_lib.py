@@ -33,7 +33,7 @@ class Col(C.Structure):
     ]
 
 
-EX_LOAD, EX_CONST, EX_PLUS, EX_MINUS, EX_MULTIPLY, EX_DIVIDE, EX_EQ, EX_NOTEQ, EX_LT, EX_LTE, EX_GT, EX_GTE, EX_AND, EX_OR, EX_NOT, EX_CAST, EX_IF, EX_IS_TRUE = range(18)
+EX_LOAD, EX_CONST, EX_PLUS, EX_MINUS, EX_MULTIPLY, EX_DIVIDE, EX_EQ, EX_NOTEQ, EX_LT, EX_LTE, EX_GT, EX_GTE, EX_AND, EX_OR, EX_NOT, EX_CAST, EX_IF, EX_IS_TRUE, EX_DT_PART, EX_DT_TRUNC = range(20)
 
 
 class ExprIns(C.Structure):
@@ -102,6 +102,19 @@ LIKE_NEGATE, LIKE_UNIT_BYTE = 1, 2
 LIKE_LONG_BYTES = 256
 
 
+class Tz(C.Structure):
+    """dbhip_tz"""
+    _fields_ = [("offset_s", C.c_int32), ("n_transitions", C.c_int32), ("at_utc_s", C.c_void_p), ("offset_after_s", C.c_void_p)]
+
+
+# dbhip_dt_part_t, dbhip_dt_unit_t and the flag of dbhip_dt_trunc
+(DT_PART_YEAR, DT_PART_QUARTER, DT_PART_MONTH, DT_PART_DAY, DT_PART_DAY_OF_YEAR, DT_PART_DOW_ISO, DT_PART_DOW_SUNDAY0, DT_PART_ISO_YEAR,
+ DT_PART_ISO_WEEK, DT_PART_HOUR, DT_PART_MINUTE, DT_PART_SECOND, DT_PART_MICROSECOND, DT_PART_EPOCH_SECOND, DT_PART_YYYYMM, DT_PART_YYYYMMDD,
+ DT_PART_YYYYMMDDHH, DT_PART_YYYYMMDDHHMMSS, DT_PART_DATE) = range(19)
+DT_UNIT_YEAR, DT_UNIT_QUARTER, DT_UNIT_MONTH, DT_UNIT_WEEK, DT_UNIT_DAY, DT_UNIT_HOUR, DT_UNIT_MINUTE, DT_UNIT_SECOND = range(8)
+DT_WEEK_SUNDAY = 1
+
+
 def library_path():
     # DBHIP_LIBRARY: another build of the same library (same-box A/B runs against an older commit's build)
     return os.environ.get("DBHIP_LIBRARY") or os.path.join(_HERE, "libdbhip.so")
@@ -127,7 +140,7 @@ SYMBOLS = [
     "dbhip_join_add_build", "dbhip_join_finalize", "dbhip_join_probe_count", "dbhip_join_probe",
     "dbhip_join_destroy", "dbhip_join_mark_build", "dbhip_join_build_matched", "dbhip_sort_perm", "dbhip_merge_sorted_perm", "dbhip_sort_bound_partition",
     "dbhip_window_bounds", "dbhip_window_rank", "dbhip_window_shift", "dbhip_window_value", "dbhip_window_aggregate",
-    "dbhip_like_kind", "dbhip_like", "dbhip_str_match", "dbhip_bitmap_set_indices", "dbhip_siphash64", "dbhip_scatter_indices", "dbhip_scatter_block", "dbhip_vec_distance", "dbhip_vec_distance_rows", "dbhip_vec_topk", "dbhip_score_u8",
+    "dbhip_like_kind", "dbhip_like", "dbhip_str_match", "dbhip_dt_part_type", "dbhip_dt_part", "dbhip_dt_trunc", "dbhip_dt_add", "dbhip_dt_diff", "dbhip_bitmap_set_indices", "dbhip_siphash64", "dbhip_scatter_indices", "dbhip_scatter_block", "dbhip_vec_distance", "dbhip_vec_distance_rows", "dbhip_vec_topk", "dbhip_score_u8",
     "dbhip_vec_topk_merge", "dbhip_vec_index_build", "dbhip_vec_index_search", "dbhip_vec_index_destroy",
     "dbhip_comm_unique_id", "dbhip_comm_create", "dbhip_comm_destroy", "dbhip_comm_abort", "dbhip_comm_allgather", "dbhip_comm_alltoall",
     "dbhip_comm_allreduce_sum_u64", "dbhip_groupby_exchange_allgather", "dbhip_groupby_exchange_alltoall", "dbhip_kmeans", "dbhip_vec_kernel_f32", "dbhip_hnsw_build", "dbhip_hnsw_build_sequential", "dbhip_hnsw_from_graph", "dbhip_hnsw_open", "dbhip_hnsw_export_graph", "dbhip_hnsw_search", "dbhip_hnsw_scores",
@@ -162,6 +175,13 @@ def load_library():
     L.dbhip_like_kind.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     L.dbhip_like.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
     L.dbhip_str_match.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
+    # the Date / Timestamp group: (part, col, tz, n, out, stream) / (unit, flags, col, out_type, tz, n, out, stream) /
+    # (unit, col, delta, tz, n, out, err_bitmap, err_count, stream) / (unit, a, b, tz, n, out, stream)
+    L.dbhip_dt_part_type.argtypes = [C.c_int32, C.c_int32]
+    L.dbhip_dt_part.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.dbhip_dt_trunc.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.dbhip_dt_add.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.dbhip_dt_diff.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     _LIB = L
     return L
 

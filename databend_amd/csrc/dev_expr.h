@@ -14,6 +14,7 @@
 // filter that precedes the maps) and whose nullable inputs feeding the node are all valid (function.rs:534-556).
 #pragma once
 #include "dev_common.h"
+#include "dev_datetime.h"
 #include "dev_decimal.h"
 #include "dev_load.h"
 
@@ -104,6 +105,8 @@ enum {
   EX_LOAD = 0, EX_CONST = 1, EX_PLUS = 2, EX_MINUS = 3, EX_MULTIPLY = 4, EX_DIVIDE = 5,
   EX_EQ = 6, EX_NOTEQ = 7, EX_LT = 8, EX_LTE = 9, EX_GT = 10, EX_GTE = 11,
   EX_AND = 12, EX_OR = 13, EX_NOT = 14, EX_CAST = 15, EX_IF = 16, EX_IS_TRUE = 17,
+  EX_DT_PART = 18, EX_DT_TRUNC = 19,  // unary, dev_datetime.h; imm (as compiled): part / unit in bits 0..7, trunc flags 8..15, bit 16 = the operand
+                                      // is a Timestamp, bit 17 = the result is one, the fixed offset in seconds (i32) in bits 32..63
   EX_DEC = 32  // internal: PLUS / MINUS / MULTIPLY / DIVIDE on decimals (the DecOp says which)
 };
 
@@ -282,6 +285,26 @@ __device__ __forceinline__ void ex_interpret(const ExProg& P, const ExProg& PA, 
           if (I.o_wide) EX_REG(I.dst + 1, k) = hi;
         }
         break;
+      case EX_DT_PART: case EX_DT_TRUNC: {
+        // The calendar functions of the stand-alone kernels (k_datetime.hip). Interpreter: the part / unit is a run-time value, so the
+        // row slots are walked by a ROLLED loop (one copy of the switch, not ROWS); specialised kernel: a constant, the switch folds.
+        const int code = (int)(I.imm & 0xFF), flags = (int)((I.imm >> 8) & 0xFF);
+        const bool ts_in = (I.imm >> 16) & 1, ts_out = (I.imm >> 17) & 1;
+        const int32_t off = (int32_t)(uint32_t)(I.imm >> 32);
+#ifdef DBHIP_JIT
+#pragma unroll
+#else
+#pragma unroll 1
+#endif
+        for (int k = 0; k < ROWS; ++k) {
+          const uint64_t x = EX_REG(I.a, k);
+          uint64_t r;
+          if (I.op == EX_DT_PART) r = ts_in ? dt_part_ts(code, (int64_t)x, off) : dt_part_date(code, (int32_t)(uint32_t)x);
+          else if (ts_in) r = ts_out ? (uint64_t)dt_trunc_ts_to_ts(code, flags, (int64_t)x, off) : (uint64_t)(int64_t)dt_trunc_ts_to_date(code, flags, (int64_t)x, off);
+          else r = ts_out ? (uint64_t)dt_trunc_date_to_ts(code, flags, (int32_t)(uint32_t)x, off) : (uint64_t)(int64_t)dt_trunc_date_to_date(code, flags, (int32_t)(uint32_t)x);
+          EX_REG(I.dst, k) = r;
+        }
+      } break;
       default:  // EX_CAST (lossless widenings only, checked on the host)
         if (I.o_wide) {
 #pragma unroll

@@ -249,7 +249,7 @@ int32_t dbhip_expr_compile_internal(const dbhip_expr_ins* prog_host, int32_t n_i
     res.type = s.type; res.loc = s.dst;
     if (s.op != DBHIP_EX_AND && s.op != DBHIP_EX_IS_TRUE && s.op != DBHIP_EX_LOAD && s.op != DBHIP_EX_CONST) {
       const int rc3 = s.op == DBHIP_EX_IF ? (int)(s.imm & 0xFF) : -1;
-      const bool unary1 = s.op == DBHIP_EX_NOT || s.op == DBHIP_EX_CAST;
+      const bool unary1 = s.op == DBHIP_EX_NOT || s.op == DBHIP_EX_CAST || s.op == DBHIP_EX_DT_PART || s.op == DBHIP_EX_DT_TRUNC;
       if ((ok_reg(s.a) && reg[s.a].strict_and) || (!unary1 && ok_reg(s.b) && reg[s.b].strict_and) || (rc3 >= 0 && ok_reg(rc3) && reg[rc3].strict_and)) {
         set_error("expression program: instruction %d consumes an AND over a nullable operand; only the filter (or another AND) may — "
                   "the reference's and / or are three-valued (evaluator.rs:284-305)", i);
@@ -396,6 +396,30 @@ int32_t dbhip_expr_compile_internal(const dbhip_expr_ins* prog_host, int32_t n_i
         ex_decode(d, ra.type, -1);
         res.dep = ra.dep; res.may_raise = ra.may_raise;
       } break;
+      case DBHIP_EX_DT_PART: case DBHIP_EX_DT_TRUNC: {
+        // group a21 with a fixed offset: never raises, NULL passes through
+        if (!ok_reg(s.a)) { set_error("expression program: instruction %d reads an unset register", i); return DBHIP_ERR_INVALID; }
+        const RegInfo& ra = reg[s.a];
+        const int code = (int)(s.imm & 0xFF), flags = (int)((s.imm >> 8) & 0xFF);
+        const int32_t off = (int32_t)(uint32_t)(s.imm >> 32);
+        const bool ts_in = ra.type == DBHIP_T_TIMESTAMP, ts_out = s.type == DBHIP_T_TIMESTAMP;
+        if ((ra.type != DBHIP_T_DATE && !ts_in) || off > DT_MAX_OFFSET_S || off < -DT_MAX_OFFSET_S || (s.imm & 0xFFFF0000ull)) {
+          set_error("expression program: instruction %d: a date function needs a Date / Timestamp register, an offset within +-64800 s and bits 16..31 of imm zero", i);
+          return DBHIP_ERR_INVALID;
+        }
+        if (s.op == DBHIP_EX_DT_PART) {
+          if (flags || dbhip_dt_part_type(code, ra.type) < 0 || dbhip_dt_part_type(code, ra.type) != s.type) {
+            set_error("expression program: instruction %d: part %d of type %d does not yield type %d", i, code, ra.type, s.type);
+            return DBHIP_ERR_INVALID;
+          }
+        } else if (code >= DTU_COUNT || (flags & ~DTF_WEEK_SUNDAY) || (s.type != DBHIP_T_DATE && !ts_out) || (code > DTU_DAY && !(ts_in && ts_out))) {
+          set_error("expression program: instruction %d: truncation to unit %d (flags %d) from type %d to type %d", i, code, flags, ra.type, s.type);
+          return DBHIP_ERR_INVALID;
+        }
+        ex_decode(d, ra.type, -1);
+        d.imm = s.imm | ((uint64_t)ts_in << 16) | ((uint64_t)ts_out << 17);
+        res.dep = ra.dep; res.may_raise = ra.may_raise;
+      } break;
       case DBHIP_EX_IF: {
         // if(cond, then, else) (evaluator.rs:284-305 evaluates the branches under the condition's validity, so an error in
         // the branch a row does not take is never raised): fused only when neither branch can raise — then it is a select
@@ -467,7 +491,7 @@ int32_t dbhip_expr_compile_internal(const dbhip_expr_ins* prog_host, int32_t n_i
       if (I.op == EX_CONST) return false;
       if (I.a == loc) return true;
       if (I.op == EX_IF && I.c == loc) return true;
-      return I.op != EX_NOT && I.op != EX_CAST && I.b == loc;
+      return I.op != EX_NOT && I.op != EX_CAST && I.op != EX_DT_PART && I.op != EX_DT_TRUNC && I.b == loc;
     };
     auto is_root = [&](int loc) { for (int r = 0; r < n_roots; ++r) if (root_loc[r] == loc) return true; return false; };
     auto live_after = [&](int i, int loc) {
@@ -489,7 +513,7 @@ int32_t dbhip_expr_compile_internal(const dbhip_expr_ins* prog_host, int32_t n_i
     for (int i = 0; i < n_out && !fail; ++i) {
       ExIns& I = P.ins[i];
       const int la = I.a, lb = I.b, lc = I.c, ld = I.dst;
-      const bool ra = reads(I, la), rb = I.op != EX_CONST && I.op != EX_NOT && I.op != EX_CAST && reads(I, lb), rc3 = I.op == EX_IF;
+      const bool ra = reads(I, la), rb = I.op != EX_CONST && I.op != EX_NOT && I.op != EX_CAST && I.op != EX_DT_PART && I.op != EX_DT_TRUNC && reads(I, lb), rc3 = I.op == EX_IF;
       const int sa = ra ? slot_of[la] : 0, sb = rb ? slot_of[lb] : 0, sc = rc3 ? slot_of[lc] : 0;
       if (ra && !live_after(i, la) && la != ld) release(la);
       if (rb && lb != la && !live_after(i, lb) && lb != ld) release(lb);

@@ -113,6 +113,10 @@ int jit_rows(const FaArgs& A) {
   // Q1 variant, 1.1 s cold PREPARE (r05 sweep: 2 -> 10.9 ms / 0.85 s, 3 -> 10.4 / 1.14, 4 -> 10.3 / 1.42, 6 -> 14.4 / 2.2, 8 -> 15.2 / 3.0)
   for (int i = 0; i < A.P.n_ins; ++i)
     if (A.P.ins[i].op == EX_DEC && dec_op_needs_division(A.P.dec[A.P.ins[i].dec_idx])) return 3;
+  // a program with calendar functions (EX_DT_PART / EX_DT_TRUNC, dev_datetime.h) carries ~20-60 VALU instructions per row and function,
+  // all unrolled per row slot: 4 slots keep 16+ bytes per column and lane in flight and the compile short (16 slots: 20+ s of hiprtc)
+  for (int i = 0; i < A.P.n_ins; ++i)
+    if (A.P.ins[i].op == EX_DT_PART || A.P.ins[i].op == EX_DT_TRUNC) return bytes >= 64 ? 3 : 4;
   return bytes >= 64 ? 3 : (bytes >= 32 ? 8 : 16);
 }
 std::string jit_meta(const FaArgs& A, bool multi = false) {

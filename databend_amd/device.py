@@ -543,6 +543,95 @@ def str_match(kind, col, needle, negate=False, n=None):
     return _match_result(col, n, out)
 
 
+class TimeZone:
+    """dbhip_tz: a fixed offset in seconds east of UTC, or offset_s before the first transition and offset_after_s[k] from at_utc_s[k]
+    (UTC seconds, strictly ascending) on. Only dt_part honours transitions; the other calls refuse them (keep the CPU closure)."""
+
+    def __init__(self, offset_s=0, at_utc_s=(), offset_after_s=()):
+        self.offset_s = int(offset_s)
+        self._at = np.ascontiguousarray(at_utc_s, dtype=np.int64)
+        self._after = np.ascontiguousarray(offset_after_s, dtype=np.int32)
+        assert len(self._at) == len(self._after)
+
+    def c(self):
+        tz = L.Tz()
+        tz.offset_s, tz.n_transitions = self.offset_s, len(self._at)
+        tz.at_utc_s = self._at.ctypes.data if len(self._at) else None
+        tz.offset_after_s = self._after.ctypes.data if len(self._after) else None
+        return tz
+
+
+def _tz_arg(tz):
+    """None (UTC) / seconds / TimeZone -> (ctypes argument, keep-alive)"""
+    if tz is None:
+        return None, None
+    ctz = (tz if isinstance(tz, TimeZone) else TimeZone(tz)).c()
+    return C.byref(ctz), (ctz, tz)
+
+
+def _same_validity(col, n, dtype, out, precision=0, scale=0):
+    """a unary result: the source's validity Bitmap at its bit offset (a scalar's one bit repeated)"""
+    if col.is_scalar:
+        return Column(dtype, n, out, _merged_validity(col, col, n), precision, scale, keep=(col,))
+    res = Column(dtype, n, out, col.validity, precision, scale, keep=(col,))
+    res.voff = col.voff
+    return res
+
+
+def dt_part_type(part, src_type):
+    """dbhip_dt_part_type: the fixed result type of a part, or -1"""
+    return lib().dbhip_dt_part_type(C.c_int32(part), C.c_int32(src_type))
+
+
+def dt_part(part, col, tz=None, n=None):
+    """EXTRACT / to_year .. to_second / to_yyyymm* / to_date(ts): one part (L.DT_PART_*) of a Date or Timestamp column -> Column of the
+    part's fixed type, the source's validity. tz: None (UTC), seconds east, or a TimeZone (transitions allowed here)."""
+    n = col.n if n is None else n
+    out_t = dt_part_type(part, col.dtype)
+    if out_t < 0:
+        raise L.DbhipError(L.ERR_INVALID, f"part {part} of a column of type {col.dtype}")
+    out = DeviceBuffer(max(n, 1) * ELEM_SIZE[out_t] + 64)
+    cc = col.c()
+    tzp, keep = _tz_arg(tz)
+    check(lib().dbhip_dt_part(C.c_int32(part), C.byref(cc), tzp, C.c_int64(n), C.c_void_p(out.ptr), None))
+    return _same_validity(col, n, out_t, out)
+
+
+def dt_trunc(unit, col, out_type=None, tz=None, week_sunday=False, n=None):
+    """date_trunc / to_start_of_* / to_timestamp(d): truncate to L.DT_UNIT_*; out_type L.T_DATE or L.T_TIMESTAMP (default: the source's)"""
+    n = col.n if n is None else n
+    out_type = col.dtype if out_type is None else out_type
+    out = DeviceBuffer(max(n, 1) * 8 + 64)
+    cc = col.c()
+    tzp, keep = _tz_arg(tz)
+    check(lib().dbhip_dt_trunc(C.c_int32(unit), C.c_int32(L.DT_WEEK_SUNDAY if week_sunday else 0), C.byref(cc), C.c_int32(out_type), tzp, C.c_int64(n),
+                               C.c_void_p(out.ptr), None))
+    return _same_validity(col, n, out_type, out)
+
+
+def dt_add(unit, col, delta, tz=None, n=None, errors=None):
+    """add_years .. add_seconds / date_add: col + delta units; delta an Int64 Column (or scalar Column). Rows that leave the range raise
+    `date out of range` into `errors` (a RowErrors) and hold 0."""
+    n = n if n is not None else max(col.n if not col.is_scalar else 0, delta.n if not delta.is_scalar else 0)
+    out = DeviceBuffer(max(n, 1) * ELEM_SIZE[col.dtype] + 64)
+    cc, cd = col.c(), delta.c()
+    tzp, keep = _tz_arg(tz)
+    eb = C.c_void_p(errors.bitmap.ptr) if errors else None
+    ec = C.c_void_p(errors.count.ptr) if errors else None
+    check(lib().dbhip_dt_add(C.c_int32(unit), C.byref(cc), C.byref(cd), tzp, C.c_int64(n), C.c_void_p(out.ptr), eb, ec, None))
+    return Column(col.dtype, n, out, _merged_validity(col, delta, n), keep=(col, delta))
+
+
+def dt_diff(unit, a, b, tz=None, n=None):
+    """date_diff(unit, a, b): boundaries crossed from a to b -> Int64 Column"""
+    n = n if n is not None else max(a.n if not a.is_scalar else 0, b.n if not b.is_scalar else 0)
+    out = DeviceBuffer(max(n, 1) * 8 + 64)
+    ca, cb = a.c(), b.c()
+    tzp, keep = _tz_arg(tz)
+    check(lib().dbhip_dt_diff(C.c_int32(unit), C.byref(ca), C.byref(cb), tzp, C.c_int64(n), C.c_void_p(out.ptr), None))
+    return Column(L.T_I64, n, out, _merged_validity(a, b, n), keep=(a, b))
+
+
 def select_cmp(op, a, b, sel=None, n=None, want_false=False):
     """Selector leaf (filter/select_value): `a op b` evaluated on the rows of `sel` (a DeviceBuffer of u32 row ids, `n` of them) or on
     all n rows; -> (true list DeviceBuffer, n_true, false list DeviceBuffer | None). NULL rows do not pass."""
@@ -813,6 +902,20 @@ class ExprProgram:
         if typ == L.T_DEC128 and not precision:
             size = (38, self.size[a][1])
         return self._emit(L.EX_CAST, a, 0, typ, release=(a,), size=size)
+
+    @staticmethod
+    def _dt_imm(code, flags, offset_s):
+        return (code & 0xFF) | ((flags & 0xFF) << 8) | ((int(offset_s) & 0xFFFFFFFF) << 32)
+
+    def dt_part(self, a, part, offset_s=0, keep=()):
+        """to_year(a) and its family at a fixed offset (DBHIP_EX_DT_PART); the result type is dbhip_dt_part_type's"""
+        typ = lib().dbhip_dt_part_type(C.c_int32(part), C.c_int32(self.types[a]))
+        return self._emit(L.EX_DT_PART, a, 0, typ, imm=self._dt_imm(part, 0, offset_s), release=() if a in keep else (a,))
+
+    def dt_trunc(self, a, unit, out_type=None, offset_s=0, week_sunday=False, keep=()):
+        """date_trunc / to_start_of_* at a fixed offset (DBHIP_EX_DT_TRUNC)"""
+        typ = self.types[a] if out_type is None else out_type
+        return self._emit(L.EX_DT_TRUNC, a, 0, typ, imm=self._dt_imm(unit, L.DT_WEEK_SUNDAY if week_sunday else 0, offset_s), release=() if a in keep else (a,))
 
     def if_(self, cond, then, other):
         return self._emit(L.EX_IF, cond, then, self.types[then], imm=other, release=(cond, then, other), size=self.size[then])

@@ -41,7 +41,7 @@ extern "C" {
 #endif
 
 #define DBHIP_ABI_VERSION 6   /* 6 (round 6): pipelined fused aggregation (dbhip_groupby_set_pipelined / dbhip_groupby_checkpoint), and (backward
-                                 compatible, same version) DELTA_(LENGTH_)BYTE_ARRAY / BYTE_STREAM_SPLIT on the device with dbhip_pq_chunk_take_arena; 5 (round 5): ZSTD on the device, batched chunk decode (dbhip_pq_chunks_decode_device); 4 (round 4): block scatter / concat, exchange and plan calls, device-mode scan, cancellation, row-wise vector distance */
+                                 compatible, same version) DELTA_(LENGTH_)BYTE_ARRAY / BYTE_STREAM_SPLIT on the device with dbhip_pq_chunk_take_arena; likewise the Date / Timestamp functions (a21: dbhip_dt_part / _trunc / _add / _diff, DBHIP_EX_DT_PART / DBHIP_EX_DT_TRUNC); 5 (round 5): ZSTD on the device, batched chunk decode (dbhip_pq_chunks_decode_device); 4 (round 4): block scatter / concat, exchange and plan calls, device-mode scan, cancellation, row-wise vector distance */
 
 /* ---- status codes ------------------------------------------------------- */
 enum {
@@ -230,9 +230,14 @@ typedef enum {
   DBHIP_EX_EQ = 6, DBHIP_EX_NOTEQ = 7, DBHIP_EX_LT = 8, DBHIP_EX_LTE = 9, DBHIP_EX_GT = 10, DBHIP_EX_GTE = 11,
   DBHIP_EX_AND = 12, DBHIP_EX_OR = 13, DBHIP_EX_NOT = 14, DBHIP_EX_CAST = 15,
   DBHIP_EX_IF = 16,      /* dst <- a ? b : register (imm & 0xFF)                     */
-  DBHIP_EX_IS_TRUE = 17  /* dst <- a is TRUE (a NULL or FALSE operand gives FALSE, the result is never NULL):
+  DBHIP_EX_IS_TRUE = 17, /* dst <- a is TRUE (a NULL or FALSE operand gives FALSE, the result is never NULL):
                           * FilterHelpers::decode_predicate (utils/filter_helper.rs), what and_filters / or_filters apply to every
                           * argument (evaluator.rs:1815-1880) — or_filters(p, q) = OR(IS_TRUE p, IS_TRUE q) */
+  DBHIP_EX_DT_PART = 18, /* dst <- part of the Date / Timestamp register a (group a21: dbhip_dt_part with a fixed offset). imm: the part
+                          * in bits 0..7, the offset in seconds as an i32 in bits 32..63; `type` must be dbhip_dt_part_type's.
+                          * Never raises; NULL passes through like CAST */
+  DBHIP_EX_DT_TRUNC = 19 /* dst <- a truncated (dbhip_dt_trunc): imm = unit in bits 0..7, the trunc flags in bits 8..15, the offset in
+                          * bits 32..63; `type` = DATE or TIMESTAMP, the same pairs as the call */
 } dbhip_expr_op;
 typedef struct {
   int32_t op;            /* dbhip_expr_op                                           */
@@ -890,6 +895,87 @@ int32_t dbhip_like(const dbhip_col* col, const uint8_t* pattern_host, int32_t pa
  * equal to the empty one. needle_len <= 255. */
 int32_t dbhip_str_match(int32_t kind, const dbhip_col* col, const uint8_t* needle_host, int32_t needle_len, int32_t flags,
                         int64_t n, uint8_t* out_bitmap, void* stream);
+/* jit-embed: resume */
+
+/* jit-embed: skip (as a19: the run-time compiled kernels never see this group; the codes they need live in csrc/dev_datetime.h) */
+/* ---- a21: Date and Timestamp functions: extract, truncate, add, diff ------------------
+ * Replaces the closures behind to_year .. to_second, to_yyyymm*, to_day_of_week / EXTRACT(DOW), to_week_of_year, to_start_of_*,
+ * date_trunc, add_* / date_add, date_diff, to_date(ts) and to_timestamp(d) (INTEGRATION.md §16 maps the names). The reference's
+ * source is not at hand, so this comment is the definition; csrc/dev_datetime.h implements it once, for these calls, for the two
+ * expression ops DBHIP_EX_DT_PART / DBHIP_EX_DT_TRUNC and for the host checker.
+ *
+ * Values. Date = i32 days since 1970-01-01 in the proleptic Gregorian calendar, valid 0001-01-01 .. 9999-12-31 = -719162 .. 2932896.
+ * Timestamp = i64 microseconds since the epoch, valid -62135596800000000 .. 253402300799999999. Every division is a FLOOR division
+ * (one microsecond before 1970 is 1969-12-31 23:59:59.999999). A value outside the valid range in a non-NULL row faults nothing; its
+ * result is unspecified for part, trunc and diff, and the row error below for add.
+ *
+ * Time zone. Only Timestamps have a local time: a Date source ignores `tz` (except Date -> Timestamp truncation, which yields local
+ * midnight). NULL = UTC. offset_s applies before the first transition, offset_after_s[k] from at_utc_s[k] on (both HOST arrays,
+ * at_utc_s strictly ascending): local_micros = utc_micros + 1e6 * offset(at floor(utc_micros / 1e6)). DBHIP_ERR_INVALID: an offset
+ * (any of them) above 64800 in magnitude, at_utc_s not strictly ascending, more than 512 transitions. The transition table is
+ * honoured by dbhip_dt_part only (UTC -> local is unambiguous); trunc, add and diff go from local time back to UTC and return
+ * DBHIP_ERR_UNSUPPORTED when n_transitions > 0 (keep the CPU closure). With a table dbhip_dt_part drains the stream before it returns
+ * (the table is caller-owned host memory); every other form is asynchronous.
+ *
+ * Parts and their fixed result types (dbhip_dt_part_type, host only, returns the dbhip_type or -1):
+ *   U16  YEAR, DAY_OF_YEAR (1..366), ISO_YEAR          U8   QUARTER, MONTH, DAY, DOW_ISO (Monday = 1 .. Sunday = 7),
+ *   U32  YYYYMM, YYYYMMDD                                   DOW_SUNDAY0 (Sunday = 0 .. Saturday = 6), ISO_WEEK (1..53, ISO 8601)
+ *   Timestamp sources only: U8 HOUR, MINUTE, SECOND; U32 MICROSECOND (0..999999); I64 EPOCH_SECOND (floor, UTC);
+ *   U64 YYYYMMDDHH (9999123123 does not fit 32 bits) and YYYYMMDDHHMMSS; DATE = the local day (to_date(ts)).
+ * A Timestamp-only part on a Date is DBHIP_ERR_INVALID. Where the reference registers a wider type the binding widens with
+ * dbhip_cast. ISO year and week are those of the Thursday of the row's week; every valid Date has an ISO year in 1..9999 (0001-01-01
+ * is a Monday, 9999-12-31 a Friday of week 52).
+ *
+ * Truncation. Units YEAR, QUARTER, MONTH, WEEK (from Monday; from Sunday with DBHIP_DT_WEEK_SUNDAY), DAY, HOUR, MINUTE, SECOND;
+ * out_type DATE or TIMESTAMP: Date -> DATE (to_start_of_month(d)), Date -> TIMESTAMP at local midnight (to_timestamp(d)),
+ * Timestamp -> TIMESTAMP (date_trunc: truncate in local time, shift back by the fixed offset), Timestamp -> DATE
+ * (to_start_of_month(ts)). HOUR / MINUTE / SECOND on a Date source or with DATE output: DBHIP_ERR_INVALID. Truncation never raises:
+ * the floor of a valid value is valid, except at the very start of year 1 — the Sunday start of the week of 0001-01-01 (a Monday),
+ * and local midnights that a non-zero offset carries out of the range — where the result is CLAMPED into the output type's range.
+ *
+ * Addition. `delta` is an I64 column or scalar. YEAR / QUARTER / MONTH: calendar addition in local time, the day of month clamped to
+ * the target month's last day (Jan 31 + 1 month = Feb 28 or 29), the time of day kept. WEEK / DAY: fixed lengths, on both types.
+ * HOUR / MINUTE / SECOND: Timestamps only (DBHIP_ERR_INVALID on a Date: the reference casts to Timestamp first). Row error
+ * "date out of range", reported like dbhip_arith's (bit i of err_bitmap — preset to ones here, ceil(n / 32) * 4 bytes — cleared,
+ * *err_count_dev incremented, the row holds 0): the result leaves the type's range, the input is outside it already, or the delta
+ * is too large for the range — decided from |delta| before any multiply, so no intermediate overflows for any i64 delta. A row whose
+ * validity bit is 0 in either operand never raises.
+ *
+ * Difference. out[i] = boundaries of `unit` crossed from a to b (negative when b < a): YEAR year(b) - year(a); QUARTER / MONTH the
+ * same on year * 4 + quarter and year * 12 + month; WEEK floor((days_b + 3) / 7) - floor((days_a + 3) / 7) (Monday boundaries); DAY
+ * the local-day difference; HOUR / MINUTE / SECOND (Timestamps only) the difference of the floor quotients of local micros. a and b
+ * have the same type; either may be a scalar.
+ *
+ * Calls. Validity passes through (the binding reuses the source's Bitmap, as for dbhip_decimal_neg); the payload is computed for all
+ * rows. is_scalar inputs are allowed. n = 0 returns DBHIP_OK. Alignment: element-aligned data on 16-byte-aligned bases, as the
+ * library's own allocations have — every lane reads and writes whole 16-byte vectors of consecutive rows; an `out` (or a non-scalar
+ * input) that is not 16-byte aligned is DBHIP_ERR_INVALID. */
+typedef struct {
+  int32_t offset_s;              /* seconds east of UTC before the first transition */
+  int32_t n_transitions;
+  const int64_t* at_utc_s;       /* host, strictly ascending                        */
+  const int32_t* offset_after_s; /* host                                            */
+} dbhip_tz;
+typedef enum {
+  DBHIP_DT_PART_YEAR = 0, DBHIP_DT_PART_QUARTER = 1, DBHIP_DT_PART_MONTH = 2, DBHIP_DT_PART_DAY = 3, DBHIP_DT_PART_DAY_OF_YEAR = 4,
+  DBHIP_DT_PART_DOW_ISO = 5, DBHIP_DT_PART_DOW_SUNDAY0 = 6, DBHIP_DT_PART_ISO_YEAR = 7, DBHIP_DT_PART_ISO_WEEK = 8,
+  DBHIP_DT_PART_HOUR = 9, DBHIP_DT_PART_MINUTE = 10, DBHIP_DT_PART_SECOND = 11, DBHIP_DT_PART_MICROSECOND = 12,
+  DBHIP_DT_PART_EPOCH_SECOND = 13, DBHIP_DT_PART_YYYYMM = 14, DBHIP_DT_PART_YYYYMMDD = 15, DBHIP_DT_PART_YYYYMMDDHH = 16,
+  DBHIP_DT_PART_YYYYMMDDHHMMSS = 17, DBHIP_DT_PART_DATE = 18
+} dbhip_dt_part_t;
+typedef enum {
+  DBHIP_DT_UNIT_YEAR = 0, DBHIP_DT_UNIT_QUARTER = 1, DBHIP_DT_UNIT_MONTH = 2, DBHIP_DT_UNIT_WEEK = 3, DBHIP_DT_UNIT_DAY = 4,
+  DBHIP_DT_UNIT_HOUR = 5, DBHIP_DT_UNIT_MINUTE = 6, DBHIP_DT_UNIT_SECOND = 7
+} dbhip_dt_unit_t;
+enum { DBHIP_DT_WEEK_SUNDAY = 1 };   /* dbhip_dt_trunc flags: weeks start on Sunday */
+
+int32_t dbhip_dt_part_type(int32_t part, int32_t src_type);    /* host only */
+int32_t dbhip_dt_part(int32_t part, const dbhip_col* src, const dbhip_tz* tz, int64_t n, void* out, void* stream);
+int32_t dbhip_dt_trunc(int32_t unit, int32_t flags, const dbhip_col* src, int32_t out_type, const dbhip_tz* tz, int64_t n, void* out,
+                       void* stream);
+int32_t dbhip_dt_add(int32_t unit, const dbhip_col* src, const dbhip_col* delta, const dbhip_tz* tz, int64_t n, void* out,
+                     uint8_t* err_bitmap, uint64_t* err_count_dev, void* stream);
+int32_t dbhip_dt_diff(int32_t unit, const dbhip_col* a, const dbhip_col* b, const dbhip_tz* tz, int64_t n, int64_t* out, void* stream);
 /* jit-embed: resume */
 
 /* ---- a17/a18: vector distance ------------------------------------------------

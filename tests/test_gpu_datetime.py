@@ -1,0 +1,445 @@
+"""GPU: the Date / Timestamp functions (include/dbhip.h a21: dbhip_dt_part / _trunc / _add / _diff and the expression ops
+DBHIP_EX_DT_PART / DBHIP_EX_DT_TRUNC). Every row of every call is asserted against tests/datetime_ref.py (numpy datetime64, itself held
+to Python's datetime by tests/test_datetime_ref_cpu.py) — exact integers, no tolerance. Every output buffer is pre-filled with 0xFF and
+is 64 bytes longer than the result: an unwritten element shows, and so does a write behind element n - 1."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from databend_amd import _lib as T
+from tests import datetime_ref as R
+
+pytestmark = pytest.mark.gpu
+
+NP_OUT = {T.T_U8: np.uint8, T.T_U16: np.uint16, T.T_U32: np.uint32, T.T_U64: np.uint64, T.T_I64: np.int64, T.T_DATE: np.int32, T.T_TIMESTAMP: np.int64}
+SRC_T = {R.SRC_DATE: T.T_DATE, R.SRC_TS: T.T_TIMESTAMP}
+PAD = 64
+
+
+def column(gpu, values, src, validity=None):
+    return gpu.Column.from_numpy(np.asarray(values).astype(np.int32 if src == R.SRC_DATE else np.int64), SRC_T[src], validity=validity)
+
+
+def scalar(gpu, value, src):
+    return gpu.Column.scalar(value, SRC_T[src])
+
+
+def tz_arg(gpu, tz):
+    """None / seconds / datetime_ref.Tz -> (pointer argument, keep-alive)"""
+    if tz is None:
+        return None, None
+    z = gpu.TimeZone(tz.offset_s, tz.at, tz.after) if isinstance(tz, R.Tz) else gpu.TimeZone(tz)
+    c = z.c()
+    return C.byref(c), (c, z)
+
+
+def filled(gpu, n, dtype):
+    buf = gpu.DeviceBuffer(n * np.dtype(dtype).itemsize + PAD)
+    T.check(T.lib().dbhip_memset(C.c_void_p(buf.ptr), 0xFF, C.c_size_t(buf.nbytes), None))
+    return buf
+
+
+def read_out(buf, n, dtype):
+    """the n results; asserts that the PAD bytes behind them still hold 0xFF"""
+    raw = buf.to_numpy(np.uint8, n * np.dtype(dtype).itemsize + PAD)
+    assert np.all(raw[n * np.dtype(dtype).itemsize:] == 0xFF), "bytes behind element n - 1 were written"
+    return raw[:n * np.dtype(dtype).itemsize].view(dtype).astype(np.int64) if dtype != np.uint64 else raw[:n * 8].view(np.uint64).astype(np.int64)
+
+
+def run_part(gpu, part, col, n, tz=None, expect=T.OK):
+    dtype = NP_OUT[gpu.dt_part_type(part, col.dtype)] if gpu.dt_part_type(part, col.dtype) >= 0 else np.uint64
+    out = filled(gpu, n, dtype)
+    cc = col.c()
+    tzp, keep = tz_arg(gpu, tz)
+    rc = T.lib().dbhip_dt_part(part, C.byref(cc), tzp, n, C.c_void_p(out.ptr), None)
+    assert rc == expect, (rc, T.lib().dbhip_last_error())
+    return read_out(out, n, dtype)
+
+
+def run_trunc(gpu, unit, flags, col, out_src, n, tz=None, expect=T.OK):
+    dtype = NP_OUT[SRC_T[out_src]]
+    out = filled(gpu, n, dtype)
+    cc = col.c()
+    tzp, keep = tz_arg(gpu, tz)
+    rc = T.lib().dbhip_dt_trunc(unit, flags, C.byref(cc), SRC_T[out_src], tzp, n, C.c_void_p(out.ptr), None)
+    assert rc == expect, (rc, T.lib().dbhip_last_error())
+    return read_out(out, n, dtype)
+
+
+def run_add(gpu, unit, col, delta, n, tz=None, expect=T.OK):
+    """-> values, error rows (bool), error count"""
+    dtype = NP_OUT[col.dtype]
+    out = filled(gpu, n, dtype)
+    errors = gpu.RowErrors(n)
+    cc, cd = col.c(), delta.c()
+    tzp, keep = tz_arg(gpu, tz)
+    rc = T.lib().dbhip_dt_add(unit, C.byref(cc), C.byref(cd), tzp, n, C.c_void_p(out.ptr), C.c_void_p(errors.bitmap.ptr), C.c_void_p(errors.count.ptr), None)
+    assert rc == expect, (rc, T.lib().dbhip_last_error())
+    bad = np.zeros(n, dtype=bool)
+    bad[errors.error_rows()] = True
+    return read_out(out, n, dtype), bad, errors.num_errors()
+
+
+def run_diff(gpu, unit, a, b, n, tz=None, expect=T.OK):
+    out = filled(gpu, n, np.int64)
+    ca, cb = a.c(), b.c()
+    tzp, keep = tz_arg(gpu, tz)
+    rc = T.lib().dbhip_dt_diff(unit, C.byref(ca), C.byref(cb), tzp, n, C.c_void_p(out.ptr), None)
+    assert rc == expect, (rc, T.lib().dbhip_last_error())
+    return read_out(out, n, np.int64)
+
+
+def same(got, exp, what):
+    exp = np.asarray(exp, dtype=np.int64)
+    assert got.shape == exp.shape, (what, got.shape, exp.shape)
+    if not np.array_equal(got, exp):
+        bad = np.nonzero(got != exp)[0]
+        raise AssertionError("%s: %d rows differ, first at %d: got %d, expected %d" % (what, len(bad), bad[0], got[bad[0]], exp[bad[0]]))
+
+
+@pytest.fixture(scope="module")
+def stamps():
+    return R.timestamp_set()
+
+
+@pytest.fixture(scope="module")
+def some_dates():
+    rng = np.random.default_rng(2105)
+    return np.concatenate([np.arange(R.DATE_MIN, R.DATE_MIN + 800), np.arange(R.DATE_MAX - 799, R.DATE_MAX + 1), rng.integers(R.DATE_MIN, R.DATE_MAX + 1, 100_003)])
+
+
+@pytest.fixture(scope="module")
+def some_stamps(stamps):
+    return stamps[:7 + 3 * 4096 + 65_536 + 1]
+
+
+# ---- parts ------------------------------------------------------------------------------------------------------------------------------
+def test_parts_of_every_date(gpu):
+    dates = R.all_dates()
+    assert len(dates) == 3_652_059
+    col = column(gpu, dates, R.SRC_DATE)
+    for p in R.DATE_PARTS:
+        same(run_part(gpu, p, col, len(dates)), R.part(p, dates, R.SRC_DATE), R.PART_NAMES[p])
+
+
+@pytest.mark.parametrize("tz", list(R.OFFSETS) + ["table"], ids=lambda z: str(z))
+def test_parts_of_timestamps(gpu, stamps, tz):
+    if tz == "table":
+        tz = R.synthetic_tz()
+        ts = np.concatenate([np.array([a * 10**6 + e for a in tz.at.tolist() for e in (-1, 0, 1, 999_999, 10**6)], dtype=np.int64), stamps])
+    else:
+        ts = stamps
+    col = column(gpu, ts, R.SRC_TS)
+    for p in range(19):
+        same(run_part(gpu, p, col, len(ts), tz), R.part(p, ts, R.SRC_TS, tz), (R.PART_NAMES[p], "table" if isinstance(tz, R.Tz) else tz))
+
+
+def test_parts_under_512_transitions(gpu):
+    big = R.Tz(60, np.arange(512, dtype=np.int64) * 1000 - 256000, (np.arange(512) % 37) * 900 - 16200)
+    probe = np.concatenate([big.at * 10**6, big.at * 10**6 - 1, [R.TS_MIN, R.TS_MAX]]).astype(np.int64)
+    same(run_part(gpu, R.YYYYMMDDHHMMSS, column(gpu, probe, R.SRC_TS), len(probe), big), R.part(R.YYYYMMDDHHMMSS, probe, R.SRC_TS, big), "512 transitions")
+
+
+# ---- lane tails and tiny shapes ---------------------------------------------------------------------------------------------------------
+TAIL_N = [0, 1, 15, 16, 17, 63, 64, 65, 1023, 1025, 4099]
+
+
+@pytest.mark.parametrize("n", TAIL_N)
+def test_lane_tails(gpu, n):
+    """one U8, one U16, one U32 and one U64 part and a truncation at every n: as a plain column, as a nullable column whose Bitmap starts
+    at bit 3 (validity passes through untouched), and as a scalar"""
+    rng = np.random.default_rng(2106 + n)
+    dates = rng.integers(R.DATE_MIN, R.DATE_MAX + 1, max(n, 1))[:n]
+    ts = rng.integers(R.TS_MIN, R.TS_MAX + 1, max(n, 1))[:n]
+    cases = [(R.DAY, R.SRC_DATE, dates), (R.YEAR, R.SRC_DATE, dates), (R.YYYYMMDD, R.SRC_DATE, dates), (R.YYYYMMDDHHMMSS, R.SRC_TS, ts), (R.HOUR, R.SRC_TS, ts)]
+    valid = rng.integers(0, 2, n + 3).astype(bool)
+    for p, src, v in cases:
+        plain = column(gpu, v if n else [0], src)
+        nullable = column(gpu, v if n else [0], src, validity=np.concatenate([valid, [True]])[:max(n, 1) + 3])
+        nullable.voff = 3
+        for col in (plain, nullable):
+            same(run_part(gpu, p, col, n, 19800), R.part(p, v, src, 19800), (R.PART_NAMES[p], n))
+        one = int(v[0]) if n else 0
+        same(run_part(gpu, p, scalar(gpu, one, src), n, 19800), R.part(p, np.full(n, one), src, 19800), (R.PART_NAMES[p], n, "scalar"))
+        if n:   # the wrapper hands the source's validity on, at its bit offset
+            res = gpu.dt_part(p, nullable, 19800, n=n)
+            assert res.validity is nullable.validity and res.voff == 3 and np.array_equal(res.validity_numpy(), valid[3:3 + n])
+            same(res.to_numpy().astype(np.int64), R.part(p, v, src, 19800), "wrapper")
+    for src, v, out in ((R.SRC_DATE, dates, R.SRC_DATE), (R.SRC_DATE, dates, R.SRC_TS), (R.SRC_TS, ts, R.SRC_TS), (R.SRC_TS, ts, R.SRC_DATE)):
+        nullable = column(gpu, v if n else [0], src, validity=np.concatenate([valid, [True]])[:max(n, 1) + 3])
+        nullable.voff = 3
+        for col in (column(gpu, v if n else [0], src), nullable):
+            same(run_trunc(gpu, R.U_MONTH, 0, col, out, n, -34200), R.trunc(R.U_MONTH, 0, v, src, out, -34200), ("trunc", src, out, n))
+        one = int(v[0]) if n else 0
+        same(run_trunc(gpu, R.U_MONTH, 0, scalar(gpu, one, src), out, n, -34200), R.trunc(R.U_MONTH, 0, np.full(n, one), src, out, -34200), ("trunc scalar", n))
+
+
+# ---- truncation -------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("offset", R.OFFSETS)
+def test_trunc(gpu, some_dates, some_stamps, offset):
+    dcol, tcol = column(gpu, some_dates, R.SRC_DATE), column(gpu, some_stamps, R.SRC_TS)
+    for unit in range(8):
+        for flags in ((0, R.WEEK_SUNDAY) if unit == R.U_WEEK else (0,)):
+            same(run_trunc(gpu, unit, flags, tcol, R.SRC_TS, len(some_stamps), offset), R.trunc(unit, flags, some_stamps, R.SRC_TS, R.SRC_TS, offset),
+                 ("ts->ts", R.UNIT_NAMES[unit], flags))
+            if unit > R.U_DAY:
+                continue
+            same(run_trunc(gpu, unit, flags, tcol, R.SRC_DATE, len(some_stamps), offset), R.trunc(unit, flags, some_stamps, R.SRC_TS, R.SRC_DATE, offset),
+                 ("ts->date", R.UNIT_NAMES[unit], flags))
+            if offset == 0:                               # (a Date has no local time: Date -> DATE does not depend on the offset)
+                same(run_trunc(gpu, unit, flags, dcol, R.SRC_DATE, len(some_dates), -34200), R.trunc(unit, flags, some_dates, R.SRC_DATE, R.SRC_DATE),
+                     ("date->date", R.UNIT_NAMES[unit], flags))
+            same(run_trunc(gpu, unit, flags, dcol, R.SRC_TS, len(some_dates), offset), R.trunc(unit, flags, some_dates, R.SRC_DATE, R.SRC_TS, offset),
+                 ("date->ts", R.UNIT_NAMES[unit], flags))
+
+
+def test_sunday_week_of_the_first_day_is_clamped(gpu):
+    first = np.arange(R.DATE_MIN, R.DATE_MIN + 8)
+    got = run_trunc(gpu, R.U_WEEK, R.WEEK_SUNDAY, column(gpu, first, R.SRC_DATE), R.SRC_DATE, 8)
+    assert got.tolist() == [R.DATE_MIN] * 6 + [R.DATE_MIN + 6] * 2          # 0001-01-01 is a Monday: its Sunday lies in year 0
+    same(got, R.trunc(R.U_WEEK, R.WEEK_SUNDAY, first, R.SRC_DATE, R.SRC_DATE), "clamp")
+    assert run_trunc(gpu, R.U_WEEK, 0, column(gpu, first, R.SRC_DATE), R.SRC_DATE, 8).tolist() == [R.DATE_MIN] * 7 + [R.DATE_MIN + 7]
+
+
+# ---- addition ---------------------------------------------------------------------------------------------------------------------------
+def check_add(gpu, unit, values, delta, src, offset, what, valid=None, delta_valid=None):
+    n = len(values)
+    col = column(gpu, values, src, validity=valid)
+    d = np.asarray(delta, dtype=np.int64).reshape(-1)
+    dcol = gpu.Column.scalar(int(d[0]), T.T_I64) if len(d) == 1 else gpu.Column.from_numpy(d, T.T_I64, validity=delta_valid)
+    got, bad, count = run_add(gpu, unit, col, dcol, n, offset)
+    exp, ebad = R.add(unit, values, d if len(d) > 1 else d[0], src, offset)
+    raises = ebad.copy()
+    for v in (valid, delta_valid):
+        if v is not None:
+            raises &= v
+    assert np.array_equal(bad, raises), (what, "error rows", int(bad.sum()), int(raises.sum()))
+    assert count == int(raises.sum()), (what, count)
+    same(got, exp, what)                                  # (an error row holds 0 whether it raised or was NULL)
+
+
+@pytest.mark.parametrize("unit", range(8))
+def test_add(gpu, some_dates, some_stamps, unit):
+    cyc = lambda n: np.array(R.ADD_DELTAS, dtype=np.int64)[np.arange(n) % len(R.ADD_DELTAS)]          # noqa: E731
+    for offset in R.OFFSETS:
+        check_add(gpu, unit, some_stamps, cyc(len(some_stamps)), R.SRC_TS, offset, ("ts column", R.UNIT_NAMES[unit], offset))
+    for delta in R.ADD_DELTAS:
+        check_add(gpu, unit, some_stamps, [delta], R.SRC_TS, 0, ("ts scalar", R.UNIT_NAMES[unit], delta))
+        if unit <= R.U_DAY:
+            check_add(gpu, unit, some_dates, [delta], R.SRC_DATE, 0, ("date scalar", R.UNIT_NAMES[unit], delta))
+    if unit <= R.U_DAY:
+        check_add(gpu, unit, some_dates, cyc(len(some_dates)), R.SRC_DATE, 0, ("date column", R.UNIT_NAMES[unit]))
+
+
+@pytest.mark.parametrize("src", [R.SRC_DATE, R.SRC_TS])
+def test_add_null_rows_never_raise(gpu, src):
+    """NULL rows whose payload lies outside the range, NULL deltas that are huge: no error; the same payloads in valid rows raise"""
+    rng = np.random.default_rng(2107)
+    n = 4099
+    lo, hi = (R.DATE_MIN, R.DATE_MAX) if src == R.SRC_DATE else (R.TS_MIN, R.TS_MAX)
+    values = rng.integers(lo, hi + 1, n)
+    values[::5] = hi + 5
+    values[1::7] = lo - 1
+    delta = rng.integers(-40, 40, n)
+    delta[::3] = 2**63 - 1
+    delta[1::11] = -2**63
+    valid, dvalid = rng.integers(0, 2, n).astype(bool), rng.integers(0, 2, n).astype(bool)
+    for unit in (R.U_MONTH, R.U_DAY):
+        check_add(gpu, unit, values, delta, src, 0, ("nulls", src, unit), valid=valid, delta_valid=dvalid)
+        check_add(gpu, unit, values, delta, src, 0, ("no nulls", src, unit))
+    # only NULL rows are out of range: nothing raises
+    values2 = np.where(valid, np.clip(values, lo, hi), hi + 5)
+    col = column(gpu, values2, src, validity=valid)
+    got, bad, count = run_add(gpu, R.U_DAY, col, gpu.Column.scalar(0, T.T_I64), n)
+    assert count == 0 and not bad.any()
+    same(got, np.where(valid, values2, 0), "null payload")
+
+
+# ---- difference -------------------------------------------------------------------------------------------------------------------------
+def test_diff(gpu, some_dates, some_stamps):
+    rng = np.random.default_rng(2108)
+    for src, v in ((R.SRC_DATE, some_dates), (R.SRC_TS, some_stamps)):
+        lo, hi = (R.DATE_MIN, R.DATE_MAX) if src == R.SRC_DATE else (R.TS_MIN, R.TS_MAX)
+        year_end = 10957 if src == R.SRC_DATE else 10957 * R.DAY_US        # 2000-01-01
+        near = np.clip(v + rng.integers(-3, 4, len(v)) * (1 if src == R.SRC_DATE else 40 * 10**6), lo, hi)
+        pairs = [(v, np.roll(v, 1)), (v, v.copy()), (v, near), (np.sort(v)[::-1].copy(), np.sort(v)),
+                 (np.array([-1, 0, year_end - 1, year_end, -1, year_end]), np.array([0, -1, year_end, year_end - 1, -1, year_end - 2]))]
+        units = range(R.U_DAY + 1) if src == R.SRC_DATE else range(8)
+        for unit in units:
+            for offset in ((0,) if src == R.SRC_DATE else (0, 19800, -64800)):
+                for a, b in pairs:
+                    same(run_diff(gpu, unit, column(gpu, a, src), column(gpu, b, src), len(a), offset), R.diff(unit, a, b, src, offset),
+                         ("diff", src, R.UNIT_NAMES[unit], offset))
+            same(run_diff(gpu, unit, scalar(gpu, year_end, src), column(gpu, v, src), len(v)), R.diff(unit, np.array([year_end]), v, src), ("scalar a", unit))
+            same(run_diff(gpu, unit, column(gpu, v, src), scalar(gpu, year_end, src), len(v)), R.diff(unit, v, np.array([year_end]), src), ("scalar b", unit))
+
+
+# ---- refusals ---------------------------------------------------------------------------------------------------------------------------
+def test_refusals_leave_the_stream_usable(gpu):
+    dates, ts = np.arange(100), np.arange(100) * 10**9
+    dcol, tcol, delta = column(gpu, dates, R.SRC_DATE), column(gpu, ts, R.SRC_TS), gpu.Column.scalar(1, T.T_I64)
+    assert gpu.dt_part_type(R.HOUR, T.T_DATE) == -1 and gpu.dt_part_type(R.YEAR, T.T_I32) == -1 and gpu.dt_part_type(19, T.T_DATE) == -1
+    assert gpu.dt_part_type(R.YEAR, T.T_DATE) == T.T_U16 and gpu.dt_part_type(R.DATE, T.T_TIMESTAMP) == T.T_DATE
+    for p in R.TIME_PARTS:
+        run_part(gpu, p, dcol, 100, expect=T.ERR_INVALID)                     # a Timestamp-only part on a Date
+    run_trunc(gpu, R.U_HOUR, 0, tcol, R.SRC_DATE, 100, expect=T.ERR_INVALID)   # HOUR to DATE
+    run_trunc(gpu, R.U_HOUR, 0, dcol, R.SRC_TS, 100, expect=T.ERR_INVALID)
+    run_add(gpu, R.U_HOUR, dcol, delta, 100, expect=T.ERR_INVALID)
+    run_diff(gpu, R.U_SECOND, dcol, dcol, 100, expect=T.ERR_INVALID)
+    run_diff(gpu, R.U_DAY, dcol, tcol, 100, expect=T.ERR_INVALID)
+    table = R.synthetic_tz()
+    run_trunc(gpu, R.U_DAY, 0, tcol, R.SRC_TS, 100, table, expect=T.ERR_UNSUPPORTED)
+    run_add(gpu, R.U_DAY, tcol, delta, 100, table, expect=T.ERR_UNSUPPORTED)
+    run_diff(gpu, R.U_DAY, tcol, tcol, 100, table, expect=T.ERR_UNSUPPORTED)
+    too_many = R.Tz(0, np.arange(513), np.zeros(513))
+    descending = R.Tz(0, [5, 5, 9], [0, 60, 120])
+    for bad in (too_many, descending, 64801, -64801, R.Tz(0, [1, 2], [0, 64801])):
+        run_part(gpu, R.HOUR, tcol, 100, bad, expect=T.ERR_INVALID)
+        run_trunc(gpu, R.U_DAY, 0, tcol, R.SRC_TS, 100, bad, expect=T.ERR_INVALID)
+        run_add(gpu, R.U_DAY, tcol, delta, 100, bad, expect=T.ERR_INVALID)
+        run_diff(gpu, R.U_DAY, tcol, tcol, 100, bad, expect=T.ERR_INVALID)
+    # an output that is not 16-byte aligned
+    out = filled(gpu, 100, np.uint16)
+    cc = dcol.c()
+    assert T.lib().dbhip_dt_part(R.YEAR, C.byref(cc), None, 100, C.c_void_p(out.ptr + 2), None) == T.ERR_INVALID
+    assert np.all(out.to_numpy(np.uint8, out.nbytes) == 0xFF)                 # refused before any launch
+    # dbhip_dt_add refuses before it presets the error bitmap
+    eb = gpu.DeviceBuffer(64)
+    T.check(T.lib().dbhip_memset(C.c_void_p(eb.ptr), 0x55, C.c_size_t(64), None))
+    cd = delta.c()
+    assert T.lib().dbhip_dt_add(R.U_DAY, C.byref(cc), C.byref(cd), None, 100, C.c_void_p(out.ptr + 4), C.c_void_p(eb.ptr), None, None) == T.ERR_INVALID
+    assert np.all(eb.to_numpy(np.uint8, 64) == 0x55) and np.all(out.to_numpy(np.uint8, out.nbytes) == 0xFF)
+    # and the stream still works
+    same(run_part(gpu, R.YEAR, dcol, 100), R.part(R.YEAR, dates, R.SRC_DATE), "after the refusals")
+    same(run_part(gpu, R.HOUR, tcol, 100, 64800), R.part(R.HOUR, ts, R.SRC_TS, 64800), "after the refusals")
+
+
+# ---- the expression ops -----------------------------------------------------------------------------------------------------------------
+D1994 = 8766          # 1994-01-01
+D1997 = 9862          # 1997-01-01
+
+
+@pytest.mark.parametrize("nullable", [False, True], ids=["plain", "nullable"])
+def test_expr_to_year_equals(gpu, nullable):
+    rng = np.random.default_rng(2109)
+    n = 70_001
+    d = np.concatenate([rng.integers(D1994, D1997, n - 4), [R.DATE_MIN, R.DATE_MAX, -1, 0]])
+    valid = rng.integers(0, 4, n) > 0 if nullable else None
+    col = column(gpu, d, R.SRC_DATE, validity=valid)
+    p = gpu.ExprProgram([col])
+    r = p.cmp(T.EX_EQ, p.dt_part(p.load(0), T.DT_PART_YEAR), p.const(1995, T.T_U16))
+    out = p.run(r)
+    exp = R.part(R.YEAR, d, R.SRC_DATE) == 1995
+    assert 0 < exp.sum() < n
+    keep = valid if nullable else np.ones(n, dtype=bool)
+    assert np.array_equal(out["values"][keep], exp[keep])
+    if nullable:
+        assert np.array_equal(out["validity"], valid)
+    # the stand-alone call agrees
+    alone = gpu.cmp(T.CMP_EQ, gpu.dt_part(T.DT_PART_YEAR, col), gpu.Column.scalar(1995, T.T_U16))
+    assert np.array_equal(alone.to_numpy()[keep], exp[keep])
+    # every part and unit through the interpreter, against the reference
+    for part in R.DATE_PARTS:
+        p = gpu.ExprProgram([col])
+        same(p.run(p.dt_part(p.load(0), part))["values"].astype(np.int64)[keep], R.part(part, d, R.SRC_DATE)[keep], ("expr", R.PART_NAMES[part]))
+    for unit in range(R.U_DAY + 1):
+        p = gpu.ExprProgram([col])
+        same(p.run(p.dt_trunc(p.load(0), unit, T.T_TIMESTAMP, offset_s=-34200, week_sunday=True))["values"][keep],
+             R.trunc(unit, R.WEEK_SUNDAY, d, R.SRC_DATE, R.SRC_TS, -34200)[keep], ("expr trunc", R.UNIT_NAMES[unit]))
+
+
+def test_expr_if_yyyymm_sum(gpu, some_stamps):
+    rng = np.random.default_rng(2110)
+    n = 70_001
+    ts = np.concatenate([rng.integers(D1994 * R.DAY_US, D1997 * R.DAY_US, n - len(some_stamps[:2000])), some_stamps[:2000]])
+    x = rng.integers(-10**6, 10**6, n)
+    for offset in (0, 19800, -64800):
+        tcol, xcol = column(gpu, ts, R.SRC_TS), gpu.Column.from_numpy(x)
+        p = gpu.ExprProgram([tcol, xcol])
+        cond = p.cmp(T.EX_GTE, p.dt_part(p.load(0), T.DT_PART_YYYYMM, offset_s=offset), p.const(199506, T.T_U32))
+        r = p.if_(cond, p.load(1), p.const(0, T.T_I64))
+        out = p.run(r, want_sum=True)
+        exp = np.where(R.part(R.YYYYMM, ts, R.SRC_TS, offset) >= 199506, x, 0)
+        same(out["values"], exp, ("if(to_yyyymm(ts) >= 199506, x, 0)", offset))
+        assert out["sum"] == int(exp.sum())
+        # every Timestamp part and unit through the interpreter
+        for part in range(19):
+            p = gpu.ExprProgram([tcol])
+            same(p.run(p.dt_part(p.load(0), part, offset_s=offset))["values"].astype(np.int64), R.part(part, ts, R.SRC_TS, offset), ("expr", R.PART_NAMES[part], offset))
+        for unit in range(8):
+            p = gpu.ExprProgram([tcol])
+            same(p.run(p.dt_trunc(p.load(0), unit, offset_s=offset))["values"], R.trunc(unit, 0, ts, R.SRC_TS, R.SRC_TS, offset), ("expr trunc", unit, offset))
+
+
+def test_expr_refusals(gpu):
+    col = column(gpu, np.arange(10), R.SRC_DATE)
+    for build in (lambda p: p._emit(T.EX_DT_PART, p.load(0), 0, T.T_U8, imm=R.YEAR),                       # YEAR is U16
+                  lambda p: p._emit(T.EX_DT_PART, p.load(0), 0, T.T_U8, imm=R.HOUR),                       # a time part of a Date
+                  lambda p: p._emit(T.EX_DT_TRUNC, p.load(0), 0, T.T_TIMESTAMP, imm=R.U_HOUR),              # HOUR of a Date
+                  lambda p: p._emit(T.EX_DT_TRUNC, p.load(0), 0, T.T_I32, imm=R.U_DAY),
+                  lambda p: p.dt_part(p.load(0), T.DT_PART_YEAR, offset_s=64801)):
+        p = gpu.ExprProgram([col])
+        r = build(p)
+        with pytest.raises(T.DbhipError) as e:
+            p.run(r)
+        assert e.value.code == T.ERR_INVALID
+
+
+def fagg_stats():
+    out = (C.c_uint64 * 3)()
+    T.check(T.lib().dbhip_fagg_stats(out))
+    return dict(jit=out[0], interpreted=out[1], pending=out[2])
+
+
+@pytest.mark.parametrize("prepare", [False, True], ids=["interpreted", "specialised"])
+def test_fused_aggregation_over_date_functions(gpu, monkeypatch, tmp_path, prepare):
+    """SELECT k, count(*), sum(if(to_year(d) = 1995, v, 0)) WHERE date_trunc(month, d) = 1995-06-01 GROUP BY k over 70,001 rows and 4
+    groups through dbhip_groupby_add_block_program — interpreted, and after prepare_program (the run-time specialised kernel: the stats
+    must show that it ran) — against add_block over columns materialised with the stand-alone calls, and against the reference"""
+    monkeypatch.setenv("DBHIP_JIT_CACHE_DIR", str(tmp_path))
+    rng = np.random.default_rng(2111)
+    n = 70_001
+    d = rng.integers(9131 + 120, 9131 + 210, n)          # 1995-05-01 .. 1995-07-29 around June 1995 (9131 = 1995-01-01)
+    d[::17] = rng.integers(D1994, D1997, len(d[::17]))
+    k = rng.integers(0, 4, n)
+    v = rng.integers(-10**9, 10**9, n)
+    month = 9131 + 151                                    # 1995-06-01
+    assert R.civil(np.array([month]))[0][0] == 1995 and R.civil(np.array([month]))[1][0] == 6 and R.civil(np.array([month]))[2][0] == 1
+    aggs = [(T.AGG_COUNT, 0, 0, 0, 0), (T.AGG_SUM, T.T_I64, 0, 0, 0)]
+    dcol, vcol, kcol = column(gpu, d, R.SRC_DATE), gpu.Column.from_numpy(v), gpu.Column.from_numpy(k)
+
+    def program():
+        p = gpu.ExprProgram([dcol, vcol])
+        f = p.cmp(T.EX_EQ, p.dt_trunc(p.load(0), T.DT_UNIT_MONTH), p.const(month, T.T_DATE))
+        arg = p.if_(p.cmp(T.EX_EQ, p.dt_part(p.load(0), T.DT_PART_YEAR), p.const(1995, T.T_U16)), p.load(1), p.const(0, T.T_I64))
+        return p, f, arg
+
+    g = gpu.GroupBy([T.T_I64], aggs, [0])
+    p, f, arg = program()
+    s0 = fagg_stats()
+    if prepare:
+        g.prepare_program([kcol], p, [None, arg], filter_reg=f)
+    g.add_block_program([kcol], p, [None, arg], n, filter_reg=f)
+    s1 = fagg_stats()
+    if prepare:
+        assert s1["jit"] > s0["jit"] and s1["interpreted"] == s0["interpreted"], (s0, s1)
+    else:
+        assert s1["interpreted"] > s0["interpreted"] and s1["jit"] == s0["jit"], (s0, s1)
+    fused = sorted(g.result())
+    g.destroy()
+    # the same through the stand-alone calls
+    fcol = gpu.cmp(T.CMP_EQ, gpu.dt_trunc(T.DT_UNIT_MONTH, dcol), gpu.Column.scalar(month, T.T_DATE))
+    year = gpu.dt_part(T.DT_PART_YEAR, dcol)
+    q = gpu.ExprProgram([year, vcol])
+    m = q.run(q.if_(q.cmp(T.EX_EQ, q.load(0), q.const(1995, T.T_U16)), q.load(1), q.const(0, T.T_I64)))["values"]
+    g2 = gpu.GroupBy([T.T_I64], aggs, [0])
+    g2.add_block([kcol], [None, gpu.Column.from_numpy(m)], n, filter=fcol)
+    alone = sorted(g2.result())
+    g2.destroy()
+    keep = R.trunc(R.U_MONTH, 0, d, R.SRC_DATE, R.SRC_DATE) == month
+    arg_ref = np.where(R.part(R.YEAR, d, R.SRC_DATE) == 1995, v, 0)
+    exp = sorted((int(key), int((keep & (k == key)).sum()), int(arg_ref[keep & (k == key)].sum())) for key in range(4))
+    assert 1000 < keep.sum() < n - 1000
+    assert [tuple(int(x) for x in r) for r in fused] == exp
+    assert [tuple(int(x) for x in r) for r in alone] == exp

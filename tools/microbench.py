@@ -424,6 +424,39 @@ def main():
         f = lambda: check(Lb.dbhip_score_u8(0, C.c_void_p(q.data_ptr()), C.c_void_p(b.data_ptr()), C.c_int64(n), dim, C.c_void_p(o.data_ptr()), None))
         report(out, f"score_u8 dot {n}x{dim}", n, "rows", alg_bytes=n * dim + 4 * n, ms=timed(f))
 
+    if want("datetime"):
+        # 256 Mi rows per case (1 GiB of Dates, 2 GiB of Timestamps: far past the Infinity Cache). The yardstick is a kernel that moves the
+        # bytes of Date -> YEAR without the calendar: dbhip_cast I32 -> U16 (4 B in, 2 B out), run next to it in the same process.
+        n = int((256 << 20) * args.scale)
+        d = ri(-719162, 2932897, n, torch.int32)
+        ts = ri(-62135596800000000, 253402300799999999, n)
+        o = torch.empty(n + 8, dtype=torch.int64, device=dev)
+        y = ri(0, 65536, n, torch.int32)          # (values a u16 holds: the cast raises no row error)
+        cd, cts, ci32 = col(d, L.T_DATE).c(), col(ts, L.T_TIMESTAMP).c(), col(y, L.T_I32).c()
+        bm = torch.empty(n // 8 + 64, dtype=torch.uint8, device=dev)
+        cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+        op = C.c_void_p(o.data_ptr())
+        tz = L.Tz()
+        tz.offset_s = 19800
+        f = lambda: check(Lb.dbhip_cast(C.byref(ci32), L.T_U16, 0, 0, C.c_int64(n), op, C.c_void_p(bm.data_ptr()), C.c_void_p(cnt.data_ptr()), None))
+        cast_ms = timed(f)
+        report(out, "yardstick: cast i32 -> u16 (+ok bitmap)", n, "rows", alg_bytes=6 * n + n // 8, ms=cast_ms)
+        f = lambda: check(Lb.dbhip_dt_part(L.DT_PART_YEAR, C.byref(cd), None, C.c_int64(n), op, None))
+        year_ms = timed(f)
+        report(out, "datetime Date -> YEAR (u16)", n, "rows", alg_bytes=6 * n, ms=year_ms,
+               note=f"YEAR / cast time ratio {year_ms[0] / cast_ms[0]:.3f} (avg), {year_ms[1] / cast_ms[1]:.3f} (best)")
+        f = lambda: check(Lb.dbhip_dt_part(L.DT_PART_YYYYMMDD, C.byref(cd), None, C.c_int64(n), op, None))
+        report(out, "datetime Date -> YYYYMMDD (u32)", n, "rows", alg_bytes=8 * n, ms=timed(f))
+        f = lambda: check(Lb.dbhip_dt_part(L.DT_PART_HOUR, C.byref(cts), C.byref(tz), C.c_int64(n), op, None))
+        report(out, "datetime Timestamp -> HOUR (u8), offset +19800 s", n, "rows", alg_bytes=9 * n, ms=timed(f))
+        f = lambda: check(Lb.dbhip_dt_trunc(L.DT_UNIT_MONTH, 0, C.byref(cts), L.T_TIMESTAMP, C.byref(tz), C.c_int64(n), op, None))
+        report(out, "datetime date_trunc(month, Timestamp), offset +19800 s", n, "rows", alg_bytes=16 * n, ms=timed(f))
+        k = D.Column.scalar(3, L.T_I64)
+        ck = k.c()
+        f = lambda: check(Lb.dbhip_dt_add(L.DT_UNIT_MONTH, C.byref(cd), C.byref(ck), None, C.c_int64(n), op, C.c_void_p(bm.data_ptr()), C.c_void_p(cnt.data_ptr()), None))
+        report(out, "datetime Date + 3 MONTH (+err bitmap)", n, "rows", alg_bytes=8 * n + n // 8, ms=timed(f))
+        del d, ts, y, o, bm
+
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         json.dump(out, open(args.out, "w"), indent=1)
