@@ -119,6 +119,16 @@ pub const DBHIP_DT_UNIT_HOUR: i32 = 5;   // dbhip_dt_unit_t
 pub const DBHIP_DT_UNIT_MINUTE: i32 = 6;   // dbhip_dt_unit_t
 pub const DBHIP_DT_UNIT_SECOND: i32 = 7;   // dbhip_dt_unit_t
 pub const DBHIP_DT_WEEK_SUNDAY: i32 = 1;
+pub const DBHIP_STR_SUBSTR: i32 = 0;   // dbhip_str_slice_op
+pub const DBHIP_STR_LEFT: i32 = 1;   // dbhip_str_slice_op
+pub const DBHIP_STR_RIGHT: i32 = 2;   // dbhip_str_slice_op
+pub const DBHIP_STR_TRIM_LEADING: i32 = 3;   // dbhip_str_slice_op
+pub const DBHIP_STR_TRIM_TRAILING: i32 = 4;   // dbhip_str_slice_op
+pub const DBHIP_STR_TRIM_BOTH: i32 = 5;   // dbhip_str_slice_op
+pub const DBHIP_STR_CONCAT: i32 = 0;   // dbhip_str_build_op
+pub const DBHIP_STR_UPPER: i32 = 1;   // dbhip_str_build_op
+pub const DBHIP_STR_LOWER: i32 = 2;   // dbhip_str_build_op
+pub const DBHIP_STR_UNIT_BYTE: i32 = 1;
 pub const DBHIP_VEC_COSINE: i32 = 0;   // dbhip_vec_metric
 pub const DBHIP_VEC_L2: i32 = 1;   // dbhip_vec_metric
 pub const DBHIP_VEC_DOT: i32 = 2;   // dbhip_vec_metric
@@ -372,6 +382,10 @@ extern "C" {
     pub fn dbhip_dt_trunc(unit: i32, flags: i32, src: *const dbhip_col, out_type: i32, tz: *const dbhip_tz, n: i64, out: *mut c_void, stream: *mut c_void) -> i32;
     pub fn dbhip_dt_add(unit: i32, src: *const dbhip_col, delta: *const dbhip_col, tz: *const dbhip_tz, n: i64, out: *mut c_void, err_bitmap: *mut u8, err_count_dev: *mut u64, stream: *mut c_void) -> i32;
     pub fn dbhip_dt_diff(unit: i32, a: *const dbhip_col, b: *const dbhip_col, tz: *const dbhip_tz, n: i64, out: *mut i64, stream: *mut c_void) -> i32;
+    pub fn dbhip_str_length(col: *const dbhip_col, flags: i32, n: i64, out: *mut u64, stream: *mut c_void) -> i32;
+    pub fn dbhip_str_slice(op: i32, col: *const dbhip_col, a: *const dbhip_col, b: *const dbhip_col, pad_host: *const u8, pad_len: i32, flags: i32, n: i64, out_views: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn dbhip_str_build_bytes(op: i32, args_host: *const dbhip_col, nargs: i32, n: i64, out_bytes_host: *mut u64, stream: *mut c_void) -> i32;
+    pub fn dbhip_str_build(op: i32, args_host: *const dbhip_col, nargs: i32, n: i64, out_views: *mut c_void, out_data: *mut u8, out_data_bytes: u64, out_validity: *mut u8, err_count_dev: *mut u64, non_ascii_count_dev: *mut u64, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_distance_rows(metric: i32, elem_type: i32, lhs: *const c_void, lhs_is_scalar: i32, rhs: *const c_void, rhs_is_scalar: i32, n: i64, dim: i32, out: *mut c_void, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_distance(metric: i32, base: *const f32, n: i64, dim: i32, queries: *const f32, nq: i32, out: *mut f32, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_topk(metric: i32, base: *const f32, n: i64, dim: i32, queries: *const f32, nq: i32, k: i32, out_idx: *mut u32, out_dist: *mut f32, stream: *mut c_void) -> i32;

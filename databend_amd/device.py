@@ -543,6 +543,108 @@ def str_match(kind, col, needle, negate=False, n=None):
     return _match_result(col, n, out)
 
 
+def str_length(col, unit_byte=False, n=None):
+    """char_length(col) in UTF-8 units (length(col) in bytes with unit_byte) -> UInt64 Column with the source's validity; 0 under NULL"""
+    n = col.n if n is None else n
+    out = DeviceBuffer(max(n, 1) * 8)
+    cc = col.c()
+    check(lib().dbhip_str_length(C.byref(cc), C.c_int32(L.STR_UNIT_BYTE if unit_byte else 0), C.c_int64(n), C.c_void_p(out.ptr), None))
+    return _same_validity(col, n, L.T_U64, out)
+
+
+def _i64_arg(x):
+    """a position / length / count: an Int64 Column, or a Python int as a scalar Column"""
+    if x is None or isinstance(x, Column):
+        return x
+    return Column.scalar(int(x), L.T_I64)
+
+
+def _str_slice(op, col, a=None, b=None, pad=b"", unit_byte=False, n=None):
+    """dbhip_str_slice -> String Column that shares col's buffer table (no byte is copied) and keeps col's validity at its bit offset"""
+    a, b = _i64_arg(a), _i64_arg(b)
+    if n is None:
+        n = col.n if not col.is_scalar else max([x.n for x in (a, b) if x is not None and not x.is_scalar], default=col.n)
+    out = DeviceBuffer(max(n, 1) * 16)
+    cc = col.c()
+    ca, cb = (a.c() if a is not None else None), (b.c() if b is not None else None)
+    buf, ln = _host_bytes(pad)
+    check(lib().dbhip_str_slice(C.c_int32(op), C.byref(cc), C.byref(ca) if ca is not None else None, C.byref(cb) if cb is not None else None, buf, C.c_int32(ln),
+                                C.c_int32(L.STR_UNIT_BYTE if unit_byte else 0), C.c_int64(n), C.c_void_p(out.ptr), None))
+    keep = tuple(x for x in (col, a, b) if x is not None)
+    if col.is_scalar:
+        res = Column(L.T_STRING, n, out, _merged_validity(col, col, n), buffers=col.buffers, keep=keep)
+    else:
+        res = Column(L.T_STRING, n, out, col.validity, buffers=col.buffers, keep=keep)
+        res.voff = col.voff
+    res.n_buffers = col.n_buffers
+    return res
+
+
+def substr(col, pos, length=None, unit_byte=False, n=None):
+    """substr / substring / mid(col, pos[, length]): pos counts units from 1, a negative pos from the end, 0 gives the empty string; pos
+    and length are Python ints or Int64 Columns"""
+    return _str_slice(L.STR_SUBSTR, col, pos, length, unit_byte=unit_byte, n=n)
+
+
+def left(col, k, unit_byte=False, n=None):
+    """left(col, k): the first k units"""
+    return _str_slice(L.STR_LEFT, col, k, unit_byte=unit_byte, n=n)
+
+
+def right(col, k, unit_byte=False, n=None):
+    """right(col, k): the last k units"""
+    return _str_slice(L.STR_RIGHT, col, k, unit_byte=unit_byte, n=n)
+
+
+def trim(col, pad=b" ", where="both", n=None):
+    """trim / ltrim / rtrim / trim_leading / trim_trailing / trim_both: whole occurrences of `pad` (up to 255 bytes) removed from the
+    start ("leading"), the end ("trailing") or both"""
+    op = {"leading": L.STR_TRIM_LEADING, "trailing": L.STR_TRIM_TRAILING, "both": L.STR_TRIM_BOTH}[where]
+    return _str_slice(op, col, pad=pad, n=n)
+
+
+def _str_build(op, args, n=None):
+    """dbhip_str_build_bytes + dbhip_str_build -> String Column with its own data buffer (kept alive by the Column) and, when an argument
+    is nullable, the AND of the arguments' validities. res.str_counters: a DeviceBuffer of two u64 — rows that did not fit (0 here: the
+    buffer is sized by the count call) and live rows that hold a byte >= 0x80."""
+    cols = []
+    for x in args:
+        if not isinstance(x, Column):
+            x = Column.strings([x.encode() if isinstance(x, str) else bytes(x)])
+            x.is_scalar = True
+        cols.append(x)
+    if n is None:
+        n = max([c.n for c in cols if not c.is_scalar], default=1)
+    arr = (Col * len(cols))(*[c.c() for c in cols])
+    nbytes = C.c_uint64(0)
+    check(lib().dbhip_str_build_bytes(C.c_int32(op), arr, C.c_int32(len(cols)), C.c_int64(n), C.byref(nbytes), None))
+    data = DeviceBuffer(nbytes.value)
+    views = DeviceBuffer(max(n, 1) * 16)
+    validity = DeviceBuffer(((n + 63) // 64) * 8) if any(c.validity is not None for c in cols) else None
+    counters = DeviceBuffer(16).zero()
+    check(lib().dbhip_str_build(C.c_int32(op), arr, C.c_int32(len(cols)), C.c_int64(n), C.c_void_p(views.ptr), C.c_void_p(data.ptr), C.c_uint64(nbytes.value),
+                                C.c_void_p(validity.ptr) if validity is not None else None, C.c_void_p(counters.ptr), C.c_void_p(counters.ptr + 8), None))
+    ptrs = DeviceBuffer.from_numpy(np.array([data.ptr], dtype=np.uint64))
+    res = Column(L.T_STRING, n, views, validity, buffers=ptrs, keep=(data,) + tuple(cols))
+    res.str_counters = counters
+    return res
+
+
+def concat(*args, n=None):
+    """concat(a, b, ...) / a || b: 1 to 8 String Columns or constants (bytes / str); NULL where any argument is NULL"""
+    return _str_build(L.STR_CONCAT, args, n)
+
+
+def upper(col, n=None):
+    """upper / ucase(col), ASCII letters only; int(res.str_counters.to_numpy(np.uint64)[1]) rows held a byte >= 0x80"""
+    return _str_build(L.STR_UPPER, [col], n)
+
+
+def lower(col, n=None):
+    """lower / lcase(col), ASCII letters only (see upper)"""
+    return _str_build(L.STR_LOWER, [col], n)
+
+
 class TimeZone:
     """dbhip_tz: a fixed offset in seconds east of UTC, or offset_s before the first transition and offset_after_s[k] from at_utc_s[k]
     (UTC seconds, strictly ascending) on. Only dt_part honours transitions; the other calls refuse them (keep the CPU closure)."""

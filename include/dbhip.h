@@ -978,6 +978,72 @@ int32_t dbhip_dt_add(int32_t unit, const dbhip_col* src, const dbhip_col* delta,
 int32_t dbhip_dt_diff(int32_t unit, const dbhip_col* a, const dbhip_col* b, const dbhip_tz* tz, int64_t n, int64_t* out, void* stream);
 /* jit-embed: resume */
 
+/* jit-embed: skip (as a19: the run-time compiled kernels never see this group; the codes the kernels use live in csrc/dev_strfn.h) */
+/* ---- a22: String functions: length, substr / left / right, trim, concat, upper / lower ----------
+ * Replaces the closures behind length / char_length, substr / substring / mid, left, right, trim / ltrim / rtrim / trim_leading /
+ * trim_trailing / trim_both, concat / ||, upper / ucase and lower / lcase (INTEGRATION.md §17 maps the names). The reference's source
+ * is not at hand, so this comment is the definition; csrc/dev_strfn.h implements the row logic once, for the kernels and for the host
+ * checker (tests/strfn_host_check.cpp).
+ *
+ * Column. `col` (and every entry of `args_host`) must be DBHIP_T_STRING, else DBHIP_ERR_INVALID; views 16-byte aligned; is_scalar is
+ * allowed; validity and validity_offset are honoured. n = 0 returns DBHIP_OK; n > 2^32 - 2 is DBHIP_ERR_INVALID. A NULL row is never
+ * dereferenced: its result is the all-zero view (0 for the length). A long view whose buffer index is >= n_buffers, or whose table
+ * entry is NULL, is never dereferenced either: its result is the empty view (0) — for the build calls the row's whole result is the
+ * empty view when any argument is such a view. Value bytes are read only with loads that lie inside the value's own naturally
+ * aligned 4-byte words, as in a20: data buffers need no padding. An inline result (len <= 12) is canonical — the bytes past len are
+ * zero — so results can be used as group keys and hash inputs as they are.
+ *
+ * Units. By default a unit is the UTF-8 unit of a20: the boundaries of a value are position 0, position len and every byte not of the
+ * form 10xxxxxx — one code point on valid UTF-8, well defined on arbitrary bytes. With DBHIP_STR_UNIT_BYTE a unit is one byte. U below
+ * is the value's unit count.
+ *
+ * dbhip_str_length. out[i] = U (char_length); with UNIT_BYTE the byte length, from the views alone. `out`: n u64, 8-byte aligned.
+ *
+ * dbhip_str_slice. The result is a sub-range of the source value: no byte is copied and no data buffer is produced. A result longer
+ * than 12 bytes is {len', the slice's first four bytes, the same buffer index, offset + start byte}: the output column shares the
+ * source's buffer table. A result of 12 bytes or fewer is inline. `a` and `b` are DBHIP_T_I64 columns or scalars whose validity is
+ * not read (the binding merges validities); out_views: n views, 16-byte aligned.
+ *   SUBSTR         a = pos, b = len (b may be a NULL pointer: to the end). pos = 0: empty. pos > 0: start unit pos - 1, empty if >= U.
+ *                  pos < 0: start unit U + pos, empty if < 0. len <= 0: empty; else min(len, U - start) units. Decided by
+ *                  comparisons before any add: every i64, INT64_MIN and INT64_MAX included, is defined.
+ *   LEFT           a = k. k <= 0: empty; else the first min(k, U) units.
+ *   RIGHT          a = k. k <= 0: empty; else the last min(k, U) units. (A negative pos and RIGHT walk from the end.)
+ *   TRIM_LEADING / TRIM_TRAILING / TRIM_BOTH   remove repeated WHOLE occurrences of the pad (pad_host, pad_len bytes, compared bytewise)
+ *                  from the start / the end / the start and then the end. pad_len 0..255; 0 gives the value unchanged; > 255 is
+ *                  DBHIP_ERR_UNSUPPORTED. trim(x) is the pad " ". a and b are ignored. trim(both 'aa' from 'aaa') = 'a'.
+ *
+ * dbhip_str_build_bytes / dbhip_str_build: results that need new bytes. args_host: nargs dbhip_col entries (a constant is an
+ * is_scalar column). CONCAT: 1..8 arguments; UPPER / LOWER: exactly 1; other counts DBHIP_ERR_INVALID. A row is live when every
+ * argument is valid there; out_validity (may be NULL) receives the live bits, LSB-first, as whole 64-bit words (ceil(n/64)*8 bytes,
+ * 8-byte aligned), the bits past n zero; a dead row has the all-zero view. _bytes drains the stream and writes to the host the total
+ * bytes of the live rows' results that are longer than 12; the caller allocates exactly that much and calls _build with the same
+ * arguments: the long results lie back to back in row order without padding and fill out_data exactly; their views are {len, first
+ * four bytes, index 0, offset}; shorter results are inline. The kernels never write at or past out_data_bytes: a row whose bytes
+ * would not fit (or would end past offset 2^32) gets the empty view and is added to *err_count_dev (may be NULL), as is a row whose
+ * total length exceeds 2^32 - 1. UPPER / LOWER map A-Z / a-z only, every other byte is copied unchanged; *non_ascii_count_dev (may
+ * be NULL) receives, added, the number of live rows that hold a byte >= 0x80 (a binding whose reference maps Unicode keeps the CPU
+ * closure when it is non-zero).
+ *
+ * Calls. Asynchronous on `stream` except dbhip_str_build_bytes; scratch comes from the (thread, stream) scratch; cancellation is
+ * polled between the launches. No lane walks more than DBHIP_LIKE_LONG_BYTES bytes of one value serially: a longer value that needs a
+ * walk (or a copy) goes through a row list in scratch (4 bytes per row of the call) to a wave-per-row pass that reads the list's
+ * length on the device.
+ * Out of scope: nullable position / length arguments, replace, repeat, lpad / rpad, reverse, split, regular expressions, Unicode case
+ * mapping and collations, string ops inside dbhip_expr_eval programs. */
+typedef enum { DBHIP_STR_SUBSTR = 0, DBHIP_STR_LEFT = 1, DBHIP_STR_RIGHT = 2, DBHIP_STR_TRIM_LEADING = 3, DBHIP_STR_TRIM_TRAILING = 4,
+               DBHIP_STR_TRIM_BOTH = 5 } dbhip_str_slice_op;
+typedef enum { DBHIP_STR_CONCAT = 0, DBHIP_STR_UPPER = 1, DBHIP_STR_LOWER = 2 } dbhip_str_build_op;
+enum { DBHIP_STR_UNIT_BYTE = 1 };   /* flags of dbhip_str_length / dbhip_str_slice: a unit is one byte */
+
+int32_t dbhip_str_length(const dbhip_col* col, int32_t flags, int64_t n, uint64_t* out, void* stream);
+int32_t dbhip_str_slice(int32_t op, const dbhip_col* col, const dbhip_col* a, const dbhip_col* b, const uint8_t* pad_host,
+                        int32_t pad_len, int32_t flags, int64_t n, void* out_views, void* stream);
+int32_t dbhip_str_build_bytes(int32_t op, const dbhip_col* args_host, int32_t nargs, int64_t n, uint64_t* out_bytes_host, void* stream);
+int32_t dbhip_str_build(int32_t op, const dbhip_col* args_host, int32_t nargs, int64_t n, void* out_views, uint8_t* out_data,
+                        uint64_t out_data_bytes, uint8_t* out_validity, uint64_t* err_count_dev, uint64_t* non_ascii_count_dev,
+                        void* stream);
+/* jit-embed: resume */
+
 /* ---- a17/a18: vector distance ------------------------------------------------
  * Replaces cosine_distance / l2_distance / inner_product / l1_distance
  * (src/common/vector/src/distance.rs:19-165) driven by
