@@ -129,6 +129,10 @@ pub const DBHIP_STR_CONCAT: i32 = 0;   // dbhip_str_build_op
 pub const DBHIP_STR_UPPER: i32 = 1;   // dbhip_str_build_op
 pub const DBHIP_STR_LOWER: i32 = 2;   // dbhip_str_build_op
 pub const DBHIP_STR_UNIT_BYTE: i32 = 1;
+pub const DBHIP_IN_NEGATE: i32 = 1;
+pub const DBHIP_IN_PATH_BITS: i32 = 0;   // dbhip_inlist_path_t
+pub const DBHIP_IN_PATH_COMPARE: i32 = 1;   // dbhip_inlist_path_t
+pub const DBHIP_IN_PATH_TABLE: i32 = 2;   // dbhip_inlist_path_t
 pub const DBHIP_VEC_COSINE: i32 = 0;   // dbhip_vec_metric
 pub const DBHIP_VEC_L2: i32 = 1;   // dbhip_vec_metric
 pub const DBHIP_VEC_DOT: i32 = 2;   // dbhip_vec_metric
@@ -136,6 +140,9 @@ pub const DBHIP_VEC_L1: i32 = 3;   // dbhip_vec_metric
 pub const DBHIP_VEC_NORM: i32 = 4;   // dbhip_vec_metric
 pub const DBHIP_ABI_VERSION: i32 = 6;
 pub const DBHIP_LIKE_LONG_BYTES: i32 = 256;
+pub const DBHIP_IN_MAX_ITEMS: i32 = 1024;
+pub const DBHIP_IN_MAX_ITEM_BYTES: i32 = 255;
+pub const DBHIP_IN_MAX_LONG_BYTES: i32 = 16384;
 
 #[repr(C)]
 pub struct dbhip_groupby { _private: [u8; 0] }
@@ -143,6 +150,8 @@ pub struct dbhip_groupby { _private: [u8; 0] }
 pub struct dbhip_join { _private: [u8; 0] }
 #[repr(C)]
 pub struct dbhip_join_binary { _private: [u8; 0] }
+#[repr(C)]
+pub struct dbhip_inlist { _private: [u8; 0] }
 #[repr(C)]
 pub struct dbhip_vec_index { _private: [u8; 0] }
 #[repr(C)]
@@ -386,6 +395,10 @@ extern "C" {
     pub fn dbhip_str_slice(op: i32, col: *const dbhip_col, a: *const dbhip_col, b: *const dbhip_col, pad_host: *const u8, pad_len: i32, flags: i32, n: i64, out_views: *mut c_void, stream: *mut c_void) -> i32;
     pub fn dbhip_str_build_bytes(op: i32, args_host: *const dbhip_col, nargs: i32, n: i64, out_bytes_host: *mut u64, stream: *mut c_void) -> i32;
     pub fn dbhip_str_build(op: i32, args_host: *const dbhip_col, nargs: i32, n: i64, out_views: *mut c_void, out_data: *mut u8, out_data_bytes: u64, out_validity: *mut u8, err_count_dev: *mut u64, non_ascii_count_dev: *mut u64, stream: *mut c_void) -> i32;
+    pub fn dbhip_inlist_create(r#type: i32, precision: u8, scale: u8, values_host: *const c_void, offsets_host: *const u32, n_items: i32, has_null: i32, out_host: *mut *mut dbhip_inlist) -> i32;
+    pub fn dbhip_inlist_path(s: *const dbhip_inlist) -> i32;
+    pub fn dbhip_inlist_eval(s: *const dbhip_inlist, col: *const dbhip_col, flags: i32, n: i64, out_bitmap: *mut u8, out_validity: *mut u8, stream: *mut c_void) -> i32;
+    pub fn dbhip_inlist_destroy(s: *mut dbhip_inlist) -> i32;
     pub fn dbhip_vec_distance_rows(metric: i32, elem_type: i32, lhs: *const c_void, lhs_is_scalar: i32, rhs: *const c_void, rhs_is_scalar: i32, n: i64, dim: i32, out: *mut c_void, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_distance(metric: i32, base: *const f32, n: i64, dim: i32, queries: *const f32, nq: i32, out: *mut f32, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_topk(metric: i32, base: *const f32, n: i64, dim: i32, queries: *const f32, nq: i32, k: i32, out_idx: *mut u32, out_dist: *mut f32, stream: *mut c_void) -> i32;

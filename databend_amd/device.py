@@ -543,6 +543,65 @@ def str_match(kind, col, needle, negate=False, n=None):
     return _match_result(col, n, out)
 
 
+class InList:
+    """A prepared constant list for `x IN (...)` (dbhip_inlist_create): `items` are the non-NULL elements — numbers (Python ints for
+    DEC128), or bytes / str for a String list; has_null says the SQL list also held a NULL. `.path` is L.IN_PATH_BITS / _COMPARE /
+    _TABLE. Raises DbhipError (ERR_UNSUPPORTED) for a list beyond the limits: plan the semi-join then."""
+
+    def __init__(self, dtype, items, has_null=False, precision=0, scale=0):
+        _ensure()
+        self.dtype, self.precision, self.scale, self.has_null = dtype, int(precision), int(scale), bool(has_null)
+        items = list(items)
+        offsets = None
+        if dtype == L.T_STRING:
+            items = [s.encode() if isinstance(s, str) else bytes(s) for s in items]
+            offsets = np.zeros(len(items) + 1, dtype=np.uint32)
+            offsets[1:] = np.cumsum([len(s) for s in items], dtype=np.uint64)
+            values = np.frombuffer(b"".join(items) or b"\0", dtype=np.uint8).copy()
+        elif dtype == L.T_DEC128:
+            values = i128_to_bytes([int(x) for x in items]) if items else np.zeros(16, np.uint8)
+        elif dtype in NP_OF:
+            values = np.array(items, dtype=NP_OF[dtype]) if items else np.zeros(1, NP_OF[dtype])
+        else:
+            values = np.zeros(32, np.uint8)      # BOOL, DEC256: refused by the library
+        values = np.ascontiguousarray(values)
+        h = C.c_void_p()
+        check(lib().dbhip_inlist_create(C.c_int32(dtype), C.c_uint8(self.precision), C.c_uint8(self.scale), values.ctypes.data_as(C.c_void_p),
+                                        offsets.ctypes.data_as(C.c_void_p) if offsets is not None else None, C.c_int32(len(items)),
+                                        C.c_int32(1 if has_null else 0), C.byref(h)))
+        self.handle = h.value
+
+    @property
+    def path(self):
+        return lib().dbhip_inlist_path(C.c_void_p(self.handle))
+
+    def destroy(self):
+        if getattr(self, "handle", None):
+            lib().dbhip_inlist_destroy(C.c_void_p(self.handle))
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def in_list(col, inlist, negate=False, n=None, want_validity=False, stream=None):
+    """col IN inlist (NOT IN with negate) -> Boolean Column whose values are the FILTER: 1 iff the SQL result is TRUE. Like like(), it
+    keeps col.validity; with want_validity its validity is the result's own (row valid AND (member OR the list held no NULL)), for a
+    caller that needs the three-valued value. `stream` is the C call's stream argument: a dbhip stream handle to queue the call on (default:
+    the library stream); the caller synchronises it before it reads the result."""
+    n, out = _match_out(col, n)
+    vout = DeviceBuffer(((n + 63) // 64) * 8 + 8) if want_validity else None
+    cc = col.c()
+    check(lib().dbhip_inlist_eval(C.c_void_p(inlist.handle), C.byref(cc), C.c_int32(L.IN_NEGATE if negate else 0), C.c_int64(n), C.c_void_p(out.ptr),
+                                  C.c_void_p(vout.ptr) if vout is not None else None, stream))
+    if want_validity:
+        return Column(L.T_BOOL, n, out, vout, keep=(col,))
+    return _match_result(col, n, out)
+
+
 def str_length(col, unit_byte=False, n=None):
     """char_length(col) in UTF-8 units (length(col) in bytes with unit_byte) -> UInt64 Column with the source's validity; 0 under NULL"""
     n = col.n if n is None else n

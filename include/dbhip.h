@@ -1044,6 +1044,65 @@ int32_t dbhip_str_build(int32_t op, const dbhip_col* args_host, int32_t nargs, i
                         void* stream);
 /* jit-embed: resume */
 
+/* jit-embed: skip (as a19: the run-time compiled kernels never see this group; the limits the kernels use are restated in csrc/dev_inlist.h) */
+/* ---- a23: constant IN-list membership: x IN (c1 .. ck), x NOT IN (..), contains([..], x) ----------
+ * Replaces, for a list of CONSTANTS, the k dbhip_cmp(EQ) + (k - 1) dbhip_bitmap_binary(OR) launches a binding had to issue (INTEGRATION.md
+ * §18 maps the names) with a prepared, device-resident set and ONE launch and ONE pass per block. The reference's source is not at
+ * hand, so this comment is the definition; csrc/dev_inlist.h implements the row logic once, for the kernels and for the host checker
+ * (tests/inlist_host_check.cpp).
+ *
+ * dbhip_inlist_create is the PREPARE step of a pipeline: synchronous, it may take its time and may drain. values_host holds the
+ * n_items non-NULL elements: for a fixed-width type n_items values of `type`; for DBHIP_T_STRING the elements' bytes back to back with
+ * offsets_host = n_items + 1 ascending byte offsets (ignored otherwise). has_null: the SQL list also held a NULL. Duplicates are
+ * allowed; n_items = 0 is allowed (IN () is FALSE for every non-NULL row). Types: I8 .. U64, F32, F64, DATE, TIMESTAMP, DEC64 and
+ * DEC128 (elements in the column's storage class and scale; eval checks col->precision / col->scale against the set's), STRING.
+ * DBHIP_ERR_UNSUPPORTED: BOOL and DEC256 (keep the CPU closure); more than DBHIP_IN_MAX_ITEMS elements, a String element beyond
+ * DBHIP_IN_MAX_ITEM_BYTES, more than DBHIP_IN_MAX_LONG_BYTES of String elements longer than 12 bytes — the binding then plans the
+ * semi-join it already has (dbhip_join_probe_mark). DBHIP_ERR_INVALID: NULL pointers with n_items > 0, descending offsets, a negative
+ * count, an unknown type. Everything the kernels need is copied into memory the handle owns: the caller's arrays are free after the
+ * call. The handle belongs to the device that was current at create.
+ *
+ * Membership. A row is a member exactly when dbhip_cmp(DBHIP_CMP_EQ, row, element) is true for some element: floats as OrderedFloat
+ * (every NaN equals every NaN, -0.0 equals +0.0; both sides are canonicalised before any hashing or bit comparison), Strings by length
+ * and bytes.
+ *
+ * Paths (dbhip_inlist_path, host only; negative -DBHIP_ERR_INVALID for a NULL set). BITS: I8 / U8 / I16 / U16, a direct bitmap of 256
+ * or 65,536 bits. COMPARE: the other types with few DISTINCT elements, each row compared against all of them. TABLE: up to 1024
+ * elements in an open-addressing table. The threshold is a constant of the library (csrc/dev_inlist.h), not a setting.
+ *
+ * dbhip_inlist_eval is asynchronous on `stream`; it never drains, allocates or copies from the host, takes no scratch, and is safe
+ * from several threads and streams on one handle at once: the handle is read-only after create. n = 0 returns DBHIP_OK; n > 2^32 - 2,
+ * a column type (or decimal precision / scale) that is not the set's, or flag bits other than DBHIP_IN_NEGATE: DBHIP_ERR_INVALID
+ * before any launch. is_scalar columns are allowed; validity and validity_offset are honoured. Column data must be element-aligned;
+ * a base that is not 16-byte aligned (a sliced column) works, as in dbhip_cmp. String views are 16-byte aligned. A long view whose
+ * buffer index is >= n_buffers, or whose table entry is NULL, is never dereferenced and is a non-member. Value bytes are read only
+ * with naturally aligned 4-byte loads that cover at least one byte of the value, as in a20: data buffers need no padding. Equality
+ * needs equal length, so no lane ever walks more than DBHIP_IN_MAX_ITEM_BYTES bytes of a value: there is no wave-per-row pass and no
+ * row list in scratch.
+ *
+ * out_bitmap is the predicate as a FILTER: LSB-first, written as whole 64-bit words (ceil(n/64)*8 bytes, 8-byte aligned, bits past n
+ * zero), the form dbhip_like, dbhip_filter_select, dbhip_bitmap_binary and dbhip_groupby_add_block_filtered take. The bit is 1 iff
+ * the SQL result is TRUE: a NULL row is never dereferenced and its bit is 0, also under DBHIP_IN_NEGATE; with has_null a non-member's
+ * result is NULL, so under DBHIP_IN_NEGATE every bit is 0. out_validity may be NULL; when given it has the same shape and holds the
+ * result's validity: row valid AND (member OR NOT has_null) — for a caller that needs the three-valued value rather than the filter.
+ *
+ * Out of scope: a selection-vector (sel_in) form; a list element that is a column or an expression; tuples (a, b) IN (..); an op
+ * inside dbhip_expr_eval programs; lists beyond the limits. */
+typedef struct dbhip_inlist dbhip_inlist;            /* opaque; belongs to the device that was current at create */
+enum { DBHIP_IN_NEGATE = 1 };                        /* NOT IN */
+typedef enum { DBHIP_IN_PATH_BITS = 0, DBHIP_IN_PATH_COMPARE = 1, DBHIP_IN_PATH_TABLE = 2 } dbhip_inlist_path_t;
+#define DBHIP_IN_MAX_ITEMS      1024
+#define DBHIP_IN_MAX_ITEM_BYTES 255                  /* one String element */
+#define DBHIP_IN_MAX_LONG_BYTES 16384                /* all String elements longer than 12 bytes together */
+
+int32_t dbhip_inlist_create(int32_t type, uint8_t precision, uint8_t scale, const void* values_host,
+                            const uint32_t* offsets_host, int32_t n_items, int32_t has_null, dbhip_inlist** out_host);
+int32_t dbhip_inlist_path(const dbhip_inlist* s);    /* host only: the dbhip_inlist_path_t this set runs on */
+int32_t dbhip_inlist_eval(const dbhip_inlist* s, const dbhip_col* col, int32_t flags, int64_t n,
+                          uint8_t* out_bitmap, uint8_t* out_validity, void* stream);
+int32_t dbhip_inlist_destroy(dbhip_inlist* s);
+/* jit-embed: resume */
+
 /* ---- a17/a18: vector distance ------------------------------------------------
  * Replaces cosine_distance / l2_distance / inner_product / l1_distance
  * (src/common/vector/src/distance.rs:19-165) driven by
