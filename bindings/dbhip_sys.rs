@@ -143,6 +143,7 @@ pub const DBHIP_LIKE_LONG_BYTES: i32 = 256;
 pub const DBHIP_IN_MAX_ITEMS: i32 = 1024;
 pub const DBHIP_IN_MAX_ITEM_BYTES: i32 = 255;
 pub const DBHIP_IN_MAX_LONG_BYTES: i32 = 16384;
+pub const DBHIP_STR_PARSE_MAX_BYTES: i32 = 256;
 
 #[repr(C)]
 pub struct dbhip_groupby { _private: [u8; 0] }
@@ -399,6 +400,9 @@ extern "C" {
     pub fn dbhip_inlist_path(s: *const dbhip_inlist) -> i32;
     pub fn dbhip_inlist_eval(s: *const dbhip_inlist, col: *const dbhip_col, flags: i32, n: i64, out_bitmap: *mut u8, out_validity: *mut u8, stream: *mut c_void) -> i32;
     pub fn dbhip_inlist_destroy(s: *mut dbhip_inlist) -> i32;
+    pub fn dbhip_str_parse(src: *const dbhip_col, dst_type: i32, dst_precision: u8, dst_scale: u8, is_try: i32, rounding_mode: i32, offset_s: i32, n: i64, out: *mut c_void, bitmap: *mut u8, err_count_dev: *mut u64, declined_count_dev: *mut u64, stream: *mut c_void) -> i32;
+    pub fn dbhip_str_format_bytes(src: *const dbhip_col, offset_s: i32, n: i64, out_bytes_host: *mut u64, stream: *mut c_void) -> i32;
+    pub fn dbhip_str_format(src: *const dbhip_col, offset_s: i32, n: i64, out_views: *mut c_void, out_data: *mut u8, out_data_bytes: u64, err_count_dev: *mut u64, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_distance_rows(metric: i32, elem_type: i32, lhs: *const c_void, lhs_is_scalar: i32, rhs: *const c_void, rhs_is_scalar: i32, n: i64, dim: i32, out: *mut c_void, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_distance(metric: i32, base: *const f32, n: i64, dim: i32, queries: *const f32, nq: i32, out: *mut f32, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_topk(metric: i32, base: *const f32, n: i64, dim: i32, queries: *const f32, nq: i32, k: i32, out_idx: *mut u32, out_dist: *mut f32, stream: *mut c_void) -> i32;

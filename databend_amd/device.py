@@ -704,6 +704,51 @@ def lower(col, n=None):
     return _str_build(L.STR_LOWER, [col], n)
 
 
+def parse_strings(col, dtype, precision=0, scale=0, is_try=False, rounding_mode=False, offset_s=0, n=None, errors=None):
+    """to_int8 .. to_uint64 / to_decimal(p, s) / to_date / to_timestamp and their try_ forms on a String column (dbhip_str_parse) ->
+    (Column, declined): `declined` is the number of rows the device did not decide (they hold 0): when it is not zero the caller
+    keeps the CPU closure for the block. A cast's row errors go into `errors` (a RowErrors) when one is given and raise otherwise; a
+    try_ cast turns them into NULLs: the Column's validity is then the call's bitmap."""
+    n = col.n if n is None else n
+    out = DeviceBuffer(max(n, 1) * ELEM_SIZE[dtype] + 64)
+    counters = DeviceBuffer(16).zero()
+    if is_try:
+        bitmap, count = DeviceBuffer(((max(n, 1) + 63) // 64) * 8), counters.ptr
+    else:
+        bitmap, count = (errors.bitmap, errors.count.ptr) if errors is not None else (None, counters.ptr)
+    cc = col.c()
+    check(lib().dbhip_str_parse(C.byref(cc), C.c_int32(dtype), C.c_uint8(precision), C.c_uint8(scale), C.c_int32(int(is_try)), C.c_int32(int(rounding_mode)),
+                                C.c_int32(offset_s), C.c_int64(n), C.c_void_p(out.ptr), C.c_void_p(bitmap.ptr) if bitmap is not None else None, C.c_void_p(count),
+                                C.c_void_p(counters.ptr + 8), None))
+    raised, declined = (int(x) for x in counters.to_numpy(np.uint64, 2))
+    if raised:
+        raise L.DbhipError(L.ERR_ROW_ERRORS, f"{raised} rows could not be parsed as type {dtype}")
+    if is_try:
+        return Column(dtype, n, out, bitmap, precision, scale, keep=(col,)), declined
+    return _same_validity(col, n, dtype, out, precision, scale), declined
+
+
+def to_string(col, offset_s=0, n=None):
+    """to_string / CAST(x AS STRING) of an integer, Decimal64 / Decimal128, Date or Timestamp column (dbhip_str_format_bytes +
+    dbhip_str_format) -> String Column with its own data buffer (kept alive by the Column) and the source's validity. res.str_counters:
+    a DeviceBuffer of one u64, the rows that got the empty view instead of a text (a Date / Timestamp outside the valid range)."""
+    n = col.n if n is None else n
+    cc = col.c()
+    nbytes = C.c_uint64(0)
+    check(lib().dbhip_str_format_bytes(C.byref(cc), C.c_int32(offset_s), C.c_int64(n), C.byref(nbytes), None))
+    data = DeviceBuffer(nbytes.value)
+    views = DeviceBuffer(max(n, 1) * 16)
+    counters = DeviceBuffer(8).zero()
+    check(lib().dbhip_str_format(C.byref(cc), C.c_int32(offset_s), C.c_int64(n), C.c_void_p(views.ptr), C.c_void_p(data.ptr), C.c_uint64(nbytes.value),
+                                 C.c_void_p(counters.ptr), None))
+    ptrs = DeviceBuffer.from_numpy(np.array([data.ptr], dtype=np.uint64))
+    res = _same_validity(col, n, L.T_STRING, views)
+    res.buffers, res.n_buffers = ptrs, 1
+    res._keep = (data, col)
+    res.str_counters = counters
+    return res
+
+
 class TimeZone:
     """dbhip_tz: a fixed offset in seconds east of UTC, or offset_s before the first transition and offset_after_s[k] from at_utc_s[k]
     (UTC seconds, strictly ascending) on. Only dt_part honours transitions; the other calls refuse them (keep the CPU closure)."""

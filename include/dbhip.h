@@ -1103,6 +1103,85 @@ int32_t dbhip_inlist_eval(const dbhip_inlist* s, const dbhip_col* col, int32_t f
 int32_t dbhip_inlist_destroy(dbhip_inlist* s);
 /* jit-embed: resume */
 
+/* jit-embed: skip (as a19: the run-time compiled kernels never see this group; the codes and the limit the kernels use are restated in csrc/dev_strcast.h) */
+/* ---- a24: String casts: parse integers, decimals, dates, timestamps; to_string ----------
+ * Replaces the closures behind to_int8 .. to_uint64, to_decimal, to_date, to_timestamp and their try_ forms on a String argument, and
+ * to_string / CAST(x AS STRING) on integers, decimals, dates and timestamps (INTEGRATION.md §19 maps the names). The reference's
+ * source is not at hand, so this comment is the definition; csrc/dev_strcast.h implements the row logic once, for the kernels and for
+ * the host checker (tests/strcast_host_check.cpp).
+ *
+ * dbhip_str_parse: String -> I8 .. U64, DEC64, DEC128, DATE, TIMESTAMP.
+ * Input. `src` must be DBHIP_T_STRING (else DBHIP_ERR_INVALID), views 16-byte aligned; is_scalar is allowed; validity and
+ * validity_offset are honoured. n = 0 returns DBHIP_OK; n > 2^32 - 2 is DBHIP_ERR_INVALID. dst_type F32 / F64 / BOOL / DEC256 (and
+ * STRING) is DBHIP_ERR_UNSUPPORTED. For DEC64 / DEC128, dst_precision is 1 .. 38, dst_scale <= dst_precision, and dst_type must be the
+ * class of the precision (DEC64 up to 18, DEC128 up to 38), else DBHIP_ERR_INVALID; both are ignored for the other targets.
+ * |offset_s| > 64800 is DBHIP_ERR_INVALID. A call that returns an error has not touched `out`.
+ * Output. `out`: n values of dst_type, element-aligned. Reporting is dbhip_cast's: `bitmap` is LSB-first, whole 64-bit words
+ * (ceil(n/64)*8 bytes, 8-byte aligned; may be NULL unless is_try). Without is_try every bit is one (the bits past n included) except
+ * at the rows that raised: a row error clears the row's bit, adds one to *err_count_dev (may be NULL) and the row holds 0. With
+ * is_try `bitmap` is the result's validity: input valid AND not a row error, the bits past n zero, and nothing is added to *err_count_dev. A
+ * NULL row is never dereferenced, never raises and holds 0. A long view whose buffer index is >= n_buffers, or whose table entry is
+ * NULL, is never dereferenced: it counts as the empty value. Value bytes are read only with naturally aligned 4-byte loads that
+ * cover at least one byte of the value, as in a20 / a22: data buffers need no padding.
+ * Whitespace. Leading and trailing bytes 0x20 and 0x09 .. 0x0D are skipped; what is left (the remainder) must match the target's
+ * grammar as a whole. An empty remainder is a row error.
+ * Declined rows. Some rows the device does not decide; they are NOT errors: the row holds 0, its bit is the input's validity (one),
+ * and it is added to *declined_count_dev (may be NULL). A binding keeps the CPU closure for the block when the count is non-zero,
+ * exactly as with non_ascii_count_dev in a22. Declined are: a value of more than DBHIP_STR_PARSE_MAX_BYTES bytes (counted before
+ * trimming; none of its bytes is read), and the forms named below. So no lane walks more than 256 bytes: one launch, one lane per
+ * row, no second pass and no scratch.
+ *   Integers    [+-]? [0-9]+ with any number of leading zeros. A '-' on an unsigned target is a row error, "-0" included. A value the
+ *               target cannot hold is the row error "number overflowed"; it is decided by a comparison before every multiply, so
+ *               nothing wraps. A remainder that does NOT match, holds '.', 'e' or 'E' and otherwise only digits and signs is declined
+ *               (reference versions differ on '1.5'::INT); every other mismatch is a row error.
+ *   Decimal(p, s)   [+-]? [0-9]* ( . [0-9]* )? with at least one digit in all. The result is the value at scale s: fraction digits
+ *               beyond s are truncated, or with rounding_mode rounded half away from zero (the first digit cut decides), the carry
+ *               included. |result| >= 10^p is the row error "Decimal overflow", kept as a sticky flag while accumulating: no
+ *               intermediate wraps for any digit string. "-0.0" is 0. After a mantissa with at least one digit, 'e' or 'E' is
+ *               declined whatever follows it; any other byte is a row error.
+ *   Date        Y{4}-M{1,2}-D{1,2}, a real day of the proleptic Gregorian calendar in 0001-01-01 .. 9999-12-31. Such a date followed by
+ *               ' ' or 'T' is declined (the reference goes through Timestamp and the session zone); a remainder made of digits only is
+ *               declined; everything else is the row error.
+ *   Timestamp   the Date form; then optionally (' ' | 'T') HH:MM ( :SS ( . [0-9]+ )? )?; then optionally 'Z', +-HH, +-HH:MM or +-HHMM.
+ *               Hours 0 .. 23, minutes and seconds 0 .. 59; the fraction's digits behind the sixth must be digits and are dropped.
+ *               Without a zone the text is local time at offset_s; a written zone replaces it and must be at most 18:00 with minutes
+ *               0 .. 59, else the row is an error. The result is UTC microseconds; one outside the Timestamp range of a21 is the row
+ *               error. A remainder made of digits only is declined. No zone names, no transition tables.
+ *
+ * dbhip_str_format_bytes / dbhip_str_format: I8 .. U64, DEC64, DEC128, DATE, TIMESTAMP -> String, by the protocol of
+ * dbhip_str_build_bytes / dbhip_str_build. F32 / F64 / BOOL / DEC256 / STRING sources are DBHIP_ERR_UNSUPPORTED; a decimal column's
+ * precision / scale outside its class, |offset_s| > 64800 and n > 2^32 - 2 are DBHIP_ERR_INVALID. Column data must be element-aligned
+ * (8 bytes are enough for DEC128: a sliced column works); is_scalar is allowed. _bytes drains the stream and writes to the host the
+ * total bytes of the live rows' results that are longer than 12; the caller allocates exactly that much and calls _format with the
+ * same arguments: the long results lie back to back in row order without padding and fill out_data exactly; their views are {len,
+ * first four bytes, index 0, offset}; shorter results are canonical inline views. Validity passes through (the binding reuses the
+ * source's bitmap): a NULL row has the all-zero view and is not counted. The kernels never write at or past out_data_bytes: a row
+ * whose bytes would not fit gets the empty view and is added to *err_count_dev (may be NULL).
+ *   Integers    the shortest decimal form, '-' for negatives (INT64_MIN included).
+ *   Decimals    sign, the integer digits ("0" when there are none), and for scale > 0 a '.' and exactly `scale` digits: "-0.50",
+ *               "0.001", "12". At most 41 bytes. A zero prints no sign.
+ *   Date        YYYY-MM-DD, zero padded: always inline.
+ *   Timestamp   YYYY-MM-DD HH:MM:SS.ffffff, local time at offset_s: always 26 bytes.
+ *   Errors      a Date / Timestamp outside a21's valid range, or a Timestamp whose local year at offset_s is not 1 .. 9999, gets the
+ *               empty view and is added to *err_count_dev.
+ * parse(format(x)) = x for every value that formats without an error (decimals: |x| < 10^precision, parsed at the column's own
+ * precision and scale).
+ *
+ * Calls. Asynchronous on `stream` except dbhip_str_format_bytes; dbhip_str_format takes 12 bytes of scratch per row from the
+ * (thread, stream) scratch and polls cancellation between its launches.
+ * Out of scope: F32 / F64 in either direction (correctly rounded float parsing and shortest float printing are a project of their own),
+ * BOOL, DEC256, exponents, zone names and transition tables, custom date formats, thousands separators, values beyond 256 bytes, casts
+ * inside dbhip_expr_eval programs. */
+#define DBHIP_STR_PARSE_MAX_BYTES 256
+
+int32_t dbhip_str_parse(const dbhip_col* src, int32_t dst_type, uint8_t dst_precision, uint8_t dst_scale, int32_t is_try,
+                        int32_t rounding_mode, int32_t offset_s, int64_t n, void* out, uint8_t* bitmap, uint64_t* err_count_dev,
+                        uint64_t* declined_count_dev, void* stream);
+int32_t dbhip_str_format_bytes(const dbhip_col* src, int32_t offset_s, int64_t n, uint64_t* out_bytes_host, void* stream);
+int32_t dbhip_str_format(const dbhip_col* src, int32_t offset_s, int64_t n, void* out_views, uint8_t* out_data,
+                         uint64_t out_data_bytes, uint64_t* err_count_dev, void* stream);
+/* jit-embed: resume */
+
 /* ---- a17/a18: vector distance ------------------------------------------------
  * Replaces cosine_distance / l2_distance / inner_product / l1_distance
  * (src/common/vector/src/distance.rs:19-165) driven by
