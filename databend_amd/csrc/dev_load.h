@@ -34,6 +34,14 @@ struct alignas(sizeof(T) * N) VecT {
   T v[N];
 };
 
+// A column pointer is only known to be aligned to its element (a slice view of an aligned buffer starts at any row): the
+// 4-element vector access is taken when the base is aligned to the vector (i0 % 4 == 0 keeps every quad aligned then), the
+// per-element path otherwise. The test reads the kernel argument alone, so it is wave-uniform.
+template <typename T>
+__device__ __forceinline__ bool vec4_aligned(const void* p) {
+  return ((unsigned long long)p & (sizeof(T) * 4 - 1)) == 0;
+}
+
 // Load 4 consecutive elements starting at i0 (i0 % 4 == 0), widened to 64 bits:
 // signed -> sign-extended, unsigned -> zero-extended, f32/f64 -> f64 bit pattern.
 template <typename T>
@@ -44,7 +52,7 @@ __device__ __forceinline__ void load4_t(const void* p, bool scalar, int64_t i0, 
   if (scalar) {
     T s = q[0];
     tmp[0] = tmp[1] = tmp[2] = tmp[3] = s;
-  } else if (i0 + 4 <= n) {
+  } else if (i0 + 4 <= n && vec4_aligned<T>(p)) {
     VecT<T, 4> v = *(const VecT<T, 4>*)(q + i0);
     tmp[0] = v.v[0]; tmp[1] = v.v[1]; tmp[2] = v.v[2]; tmp[3] = v.v[3];
   } else {
@@ -85,7 +93,7 @@ __device__ __forceinline__ void load4_wide(const void* p, int type, bool scalar,
 template <typename T>
 __device__ __forceinline__ void store4_t(void* p, int64_t i0, int64_t n, const T vals[4]) {
   T* q = (T*)p;
-  if (i0 + 4 <= n) {
+  if (i0 + 4 <= n && vec4_aligned<T>(p)) {
     VecT<T, 4> v;
     v.v[0] = vals[0]; v.v[1] = vals[1]; v.v[2] = vals[2]; v.v[3] = vals[3];
     *(VecT<T, 4>*)(q + i0) = v;

@@ -47,8 +47,9 @@ __device__ __forceinline__ i128 load_operand(const void* p, int type, bool scala
 }
 
 __device__ __forceinline__ void dec_raise(const DecParams& p, int64_t row) {
-  if (p.a_validity && !bit_get(p.a_validity, p.a_voff + row)) return;
-  if (p.b_validity && !bit_get(p.b_validity, p.b_voff + row)) return;
+  // a scalar operand has ONE validity bit, at its offset
+  if (p.a_validity && !bit_get(p.a_validity, p.a_voff + (p.a_scalar ? 0 : row))) return;
+  if (p.b_validity && !bit_get(p.b_validity, p.b_voff + (p.b_scalar ? 0 : row))) return;
   if (p.err_words) atomicAnd(&p.err_words[row >> 5], ~(1u << (row & 31)));
   if (p.err_count) atomicAdd(p.err_count, 1ULL);
 }

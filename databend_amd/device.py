@@ -169,7 +169,8 @@ class Column:
         self.buffers = buffers  # DeviceBuffer holding an array of device pointers (strings)
         self.n_buffers = 1 if buffers is not None else 0
         self.voff = 0           # bit offset of the validity Bitmap (a sliced Bitmap, bitmap/immutable.rs:78-85)
-        self.boff = 0           # bit offset of a Boolean column's VALUES (only dbhip_concat_columns reads sliced Boolean values)
+        self.boff = 0           # bit offset of a Boolean column's VALUES: dbhip_col has no field for it, c() realigns them
+        self._dense = None      # the values of a sliced Boolean column as a Bitmap at bit 0 (made on first use)
         self._keep = keep
 
     # ---- constructors -----------------------------------------------------------------
@@ -229,11 +230,22 @@ class Column:
         return cls(L.T_STRING, len(views), DeviceBuffer.from_numpy(views))
 
     # ---- access ---------------------------------------------------------------------------
-    def c(self):
+    def bits(self):
+        """a Boolean column's values as a Bitmap that starts at bit 0 (a sliced one is realigned on the device, once)"""
+        assert self.dtype == L.T_BOOL
+        if not self.boff:
+            return self.data
+        if self._dense is None:
+            self._dense = _bits_at_zero(self.data, self.boff, self.n)
+        return self._dense
+
+    def c(self, raw_bool=False):
+        """the dbhip_col of this Column. raw_bool: a sliced Boolean column's data pointer as it is (for entries that take its bit
+        offset beside the column, dbhip_concat_columns)"""
         col = Col()
         col.type = self.dtype
         col.is_scalar = 1 if self.is_scalar else 0
-        col.data = self.data.ptr
+        col.data = self.bits().ptr if self.dtype == L.T_BOOL and not raw_bool else self.data.ptr
         col.validity = self.validity.ptr if self.validity is not None else None
         col.validity_offset = self.voff
         col.buffers = self.buffers.ptr if self.buffers is not None else None
@@ -335,9 +347,31 @@ def bytes_to_i128(raw):
     return out
 
 
-def _cols(cols):
-    arr = (Col * len(cols))(*[c.c() for c in cols])
+def _cols(cols, raw_bool=False):
+    arr = (Col * len(cols))(*[c.c(raw_bool) for c in cols])
     return arr
+
+
+def _bits_at_zero(buf, off, n):
+    """bits [off, off + n) of a Bitmap as a Bitmap of their own at bit 0: the entries that take a bare Bitmap pointer (dbhip_bitmap_binary,
+    dbhip_join_*) know no offset. dbhip_take_bitmap with the identity selection does the shift on the device."""
+    if not off:
+        return buf
+    sel = DeviceBuffer.from_numpy(np.arange(max(n, 1), dtype=np.uint32))
+    out = DeviceBuffer(((max(n, 1) + 63) // 64) * 8 + 8)
+    check(lib().dbhip_take_bitmap(C.c_void_p(buf.ptr), C.c_int64(off), C.c_void_p(sel.ptr), C.c_int64(n), C.c_void_p(out.ptr), None))
+    return out
+
+
+def _validity_at_zero(col):
+    """the validity Bitmap of a non-scalar Column (or of PackedKeys, which have no offset) at bit 0, or None"""
+    return _bits_at_zero(col.validity, getattr(col, "voff", 0), col.n) if col.validity is not None else None
+
+
+def _nullable(col, vv):
+    """attach (Bitmap, bit offset) of _merged_validity to a result Column"""
+    col.validity, col.voff = vv
+    return col
 
 
 class RowErrors:
@@ -357,26 +391,26 @@ class RowErrors:
 
 
 def _merged_validity(a, b, n):
-    if a.validity is None and b.validity is None:
-        return None
-    if a.validity is None or (a.is_scalar and a.validity_numpy()[0]):
-        va = None
-    else:
-        va = a
+    """-> (Bitmap | None, its bit offset): one nullable input hands on its own Bitmap AT ITS OFFSET (the result keeps the input alive);
+    two are realigned to bit 0 and AND-ed (dbhip_bitmap_binary takes no offsets)"""
     # validity = AND of inputs (passthrough_nullable, register_vectorize.rs:447-471), on device
     bits = []
     for x in (a, b):
         if x.validity is None:
             continue
         if x.is_scalar:
-            bits.append(DeviceBuffer.from_numpy(pack_bits(np.repeat(x.validity_numpy()[:1], n))))
+            bits.append((DeviceBuffer.from_numpy(pack_bits(np.repeat(x.validity_numpy()[:1], n))), 0))
         else:
-            bits.append(x.validity)
+            bits.append((x.validity, x.voff))
+    if not bits:
+        return None, 0
     if len(bits) == 1:
         return bits[0]
+    (va, oa), (vb, ob) = bits
+    va, vb = _bits_at_zero(va, oa, n), _bits_at_zero(vb, ob, n)
     out = DeviceBuffer(((n + 63) // 64) * 8)
-    check(lib().dbhip_bitmap_binary(0, C.c_void_p(bits[0].ptr), C.c_void_p(bits[1].ptr), C.c_int64(n), C.c_void_p(out.ptr), None))
-    return out
+    check(lib().dbhip_bitmap_binary(0, C.c_void_p(va.ptr), C.c_void_p(vb.ptr), C.c_int64(n), C.c_void_p(out.ptr), None))
+    return out, 0
 
 
 def arith(op, a, b, n=None, errors=None):
@@ -390,7 +424,7 @@ def arith(op, a, b, n=None, errors=None):
     eb = C.c_void_p(errors.bitmap.ptr) if errors else None
     ec = C.c_void_p(errors.count.ptr) if errors else None
     check(lib().dbhip_arith(op, C.byref(ca), C.byref(cb), C.c_int64(n), out_t, C.c_void_p(out.ptr), eb, ec, None))
-    return Column(out_t, n, out, _merged_validity(a, b, n))
+    return _nullable(Column(out_t, n, out, keep=(a, b)), _merged_validity(a, b, n))
 
 
 def cast(col, dst_type, is_try=False, rounding_mode=True, n=None):
@@ -405,8 +439,8 @@ def cast(col, dst_type, is_try=False, rounding_mode=True, n=None):
     check(lib().dbhip_cast(C.byref(cc), dst_type, int(is_try), int(rounding_mode), C.c_int64(n), C.c_void_p(out.ptr), C.c_void_p(bm.ptr),
                            C.c_void_p(cnt.ptr), None))
     ok = unpack_bits(bm.to_numpy(np.uint8, (n + 7) // 8), n) if n else np.zeros(0, dtype=bool)
-    validity = bm if is_try else col.validity
-    return Column(dst_type, n, out, validity, keep=(col,)), ok, int(cnt.to_numpy(np.uint64, 1)[0])
+    res = Column(dst_type, n, out, bm, keep=(col,)) if is_try else _same_validity(col, n, dst_type, out)
+    return res, ok, int(cnt.to_numpy(np.uint64, 1)[0])
 
 
 def decimal_result_size(op, a, b):
@@ -428,7 +462,7 @@ def decimal_arith(op, a, b, n=None, errors=None):
     eb = C.c_void_p(errors.bitmap.ptr) if errors else None
     ec = C.c_void_p(errors.count.ptr) if errors else None
     check(lib().dbhip_decimal_arith(op, C.byref(ca), C.byref(cb), C.c_int64(n), out_t, p, s, C.c_void_p(out.ptr), eb, ec, None))
-    return Column(out_t, n, out, _merged_validity(a, b, n), p, s)
+    return _nullable(Column(out_t, n, out, None, p, s, keep=(a, b)), _merged_validity(a, b, n))
 
 
 def decimal_neg(col, n=None):
@@ -437,7 +471,7 @@ def decimal_neg(col, n=None):
     out = DeviceBuffer(max(n, 1) * ELEM_SIZE[col.dtype] + 64)
     cc = col.c()
     check(lib().dbhip_decimal_neg(C.byref(cc), C.c_int64(n), C.c_void_p(out.ptr), None))
-    return Column(col.dtype, n, out, col.validity, col.precision, col.scale, keep=(col,))
+    return _same_validity(col, n, col.dtype, out, col.precision, col.scale)
 
 
 def decimal_cast(col, precision, scale, is_try=False, rounding_mode=False, n=None):
@@ -452,7 +486,8 @@ def decimal_cast(col, precision, scale, is_try=False, rounding_mode=False, n=Non
     check(lib().dbhip_decimal_cast(C.byref(cc), dst_type, precision, scale, int(is_try), int(rounding_mode), C.c_int64(n), C.c_void_p(out.ptr),
                                    C.c_void_p(bm.ptr), C.c_void_p(cnt.ptr), None))
     ok = unpack_bits(bm.to_numpy(np.uint8, (n + 7) // 8), n) if n else np.zeros(0, dtype=bool)
-    return Column(dst_type, n, out, bm if is_try else col.validity, precision, scale, keep=(col,)), ok, int(cnt.to_numpy(np.uint64, 1)[0])
+    res = Column(dst_type, n, out, bm, precision, scale, keep=(col,)) if is_try else _same_validity(col, n, dst_type, out, precision, scale)
+    return res, ok, int(cnt.to_numpy(np.uint64, 1)[0])
 
 
 def cmp(op, a, b, n=None):
@@ -460,14 +495,14 @@ def cmp(op, a, b, n=None):
     out = DeviceBuffer(((n + 63) // 64) * 8 + 8)
     ca, cb = a.c(), b.c()
     check(lib().dbhip_cmp(op, C.byref(ca), C.byref(cb), C.c_int64(n), C.c_void_p(out.ptr), None))
-    return Column(L.T_BOOL, n, out, _merged_validity(a, b, n))
+    return _nullable(Column(L.T_BOOL, n, out, keep=(a, b)), _merged_validity(a, b, n))
 
 
 def filter_select(pred):
     """Boolean column -> ascending u32 selection vector (device) and its length."""
     sel = DeviceBuffer(max(pred.n, 1) * 4 + 64)
     cnt = DeviceBuffer(8)
-    check(lib().dbhip_filter_select(C.c_void_p(pred.data.ptr), C.c_int64(0), C.c_int64(pred.n), C.c_void_p(sel.ptr), C.c_void_p(cnt.ptr), None))
+    check(lib().dbhip_filter_select(C.c_void_p(pred.data.ptr), C.c_int64(pred.boff), C.c_int64(pred.n), C.c_void_p(sel.ptr), C.c_void_p(cnt.ptr), None))
     k = int(cnt.to_numpy(np.uint64, 1)[0])
     return sel, k
 
@@ -475,7 +510,7 @@ def filter_select(pred):
 def bitmap_count(pred, n):
     """number of set bits of a Boolean column (Bitmap::true_count)"""
     out = DeviceBuffer(8)
-    check(lib().dbhip_bitmap_count(C.c_void_p(pred.data.ptr), C.c_int64(0), C.c_int64(n), C.c_void_p(out.ptr), None))
+    check(lib().dbhip_bitmap_count(C.c_void_p(pred.data.ptr), C.c_int64(pred.boff), C.c_int64(n), C.c_void_p(out.ptr), None))
     return int(out.to_numpy(np.uint64, 1)[0])
 
 
@@ -515,7 +550,7 @@ def _match_out(col, n):
 def _match_result(col, n, out):
     """the Boolean result of a string predicate: the column's own validity Bitmap, at its bit offset"""
     if col.is_scalar:
-        return Column(L.T_BOOL, n, out, _merged_validity(col, col, n), keep=(col,))
+        return _nullable(Column(L.T_BOOL, n, out, keep=(col,)), _merged_validity(col, col, n))
     res = Column(L.T_BOOL, n, out, col.validity, keep=(col,))
     res.voff = col.voff
     return res
@@ -631,7 +666,7 @@ def _str_slice(op, col, a=None, b=None, pad=b"", unit_byte=False, n=None):
                                 C.c_int32(L.STR_UNIT_BYTE if unit_byte else 0), C.c_int64(n), C.c_void_p(out.ptr), None))
     keep = tuple(x for x in (col, a, b) if x is not None)
     if col.is_scalar:
-        res = Column(L.T_STRING, n, out, _merged_validity(col, col, n), buffers=col.buffers, keep=keep)
+        res = _nullable(Column(L.T_STRING, n, out, buffers=col.buffers, keep=keep), _merged_validity(col, col, n))
     else:
         res = Column(L.T_STRING, n, out, col.validity, buffers=col.buffers, keep=keep)
         res.voff = col.voff
@@ -778,7 +813,7 @@ def _tz_arg(tz):
 def _same_validity(col, n, dtype, out, precision=0, scale=0):
     """a unary result: the source's validity Bitmap at its bit offset (a scalar's one bit repeated)"""
     if col.is_scalar:
-        return Column(dtype, n, out, _merged_validity(col, col, n), precision, scale, keep=(col,))
+        return _nullable(Column(dtype, n, out, None, precision, scale, keep=(col,)), _merged_validity(col, col, n))
     res = Column(dtype, n, out, col.validity, precision, scale, keep=(col,))
     res.voff = col.voff
     return res
@@ -825,7 +860,7 @@ def dt_add(unit, col, delta, tz=None, n=None, errors=None):
     eb = C.c_void_p(errors.bitmap.ptr) if errors else None
     ec = C.c_void_p(errors.count.ptr) if errors else None
     check(lib().dbhip_dt_add(C.c_int32(unit), C.byref(cc), C.byref(cd), tzp, C.c_int64(n), C.c_void_p(out.ptr), eb, ec, None))
-    return Column(col.dtype, n, out, _merged_validity(col, delta, n), keep=(col, delta))
+    return _nullable(Column(col.dtype, n, out, keep=(col, delta)), _merged_validity(col, delta, n))
 
 
 def dt_diff(unit, a, b, tz=None, n=None):
@@ -835,7 +870,7 @@ def dt_diff(unit, a, b, tz=None, n=None):
     ca, cb = a.c(), b.c()
     tzp, keep = _tz_arg(tz)
     check(lib().dbhip_dt_diff(C.c_int32(unit), C.byref(ca), C.byref(cb), tzp, C.c_int64(n), C.c_void_p(out.ptr), None))
-    return Column(L.T_I64, n, out, _merged_validity(a, b, n), keep=(a, b))
+    return _nullable(Column(L.T_I64, n, out, keep=(a, b)), _merged_validity(a, b, n))
 
 
 def select_cmp(op, a, b, sel=None, n=None, want_false=False):
@@ -924,7 +959,7 @@ def take(col, sel, k):
     """DataBlock::take for one column (kernels/take.rs:43)."""
     if col.dtype == L.T_BOOL:
         out = DeviceBuffer(((k + 63) // 64) * 8 + 8)
-        check(lib().dbhip_take_bitmap(C.c_void_p(col.data.ptr), C.c_int64(0), C.c_void_p(sel.ptr), C.c_int64(k), C.c_void_p(out.ptr), None))
+        check(lib().dbhip_take_bitmap(C.c_void_p(col.data.ptr), C.c_int64(col.boff), C.c_void_p(sel.ptr), C.c_int64(k), C.c_void_p(out.ptr), None))
     else:
         es = ELEM_SIZE[col.dtype]
         out = DeviceBuffer(max(k, 1) * es + 64)
@@ -932,7 +967,7 @@ def take(col, sel, k):
     vb = None
     if col.validity is not None:
         vb = DeviceBuffer(((k + 63) // 64) * 8 + 8)
-        check(lib().dbhip_take_bitmap(C.c_void_p(col.validity.ptr), C.c_int64(0), C.c_void_p(sel.ptr), C.c_int64(k), C.c_void_p(vb.ptr), None))
+        check(lib().dbhip_take_bitmap(C.c_void_p(col.validity.ptr), C.c_int64(col.voff), C.c_void_p(sel.ptr), C.c_int64(k), C.c_void_p(vb.ptr), None))
     return Column(col.dtype, k, out, vb, col.precision, col.scale, buffers=col.buffers, keep=(col,))
 
 
@@ -958,7 +993,7 @@ def take_block(cols, sel, k):
         vb = None
         if c.validity is not None:
             vb = DeviceBuffer(((k + 63) // 64) * 8 + 8)
-            check(lib().dbhip_take_bitmap(C.c_void_p(c.validity.ptr), C.c_int64(0), C.c_void_p(sel.ptr), C.c_int64(k), C.c_void_p(vb.ptr), None))
+            check(lib().dbhip_take_bitmap(C.c_void_p(c.validity.ptr), C.c_int64(c.voff), C.c_void_p(sel.ptr), C.c_int64(k), C.c_void_p(vb.ptr), None))
         res.append(Column(c.dtype, k, outs[id(c)], vb, c.precision, c.scale, buffers=c.buffers, keep=(c,)))
     return res
 
@@ -985,7 +1020,7 @@ def take_chunks(cols, pairs):
     n = len(pr)
     dp = DeviceBuffer.from_numpy(pr.reshape(-1)) if n else DeviceBuffer(16)
     c0 = cols[0]
-    ptrs = (C.c_void_p * len(cols))(*[c.data.ptr for c in cols])
+    ptrs = (C.c_void_p * len(cols))(*[(c.bits() if c.dtype == L.T_BOOL else c.data).ptr for c in cols])
     if c0.dtype == L.T_BOOL:
         out = DeviceBuffer(((n + 63) // 64) * 8 + 8)
         check(lib().dbhip_take_chunks(ptrs, len(cols), 0, C.c_void_p(dp.ptr), C.c_int64(n), C.c_void_p(out.ptr), None))
@@ -995,7 +1030,8 @@ def take_chunks(cols, pairs):
         check(lib().dbhip_take_chunks(ptrs, len(cols), es, C.c_void_p(dp.ptr), C.c_int64(n), C.c_void_p(out.ptr), None))
     vb = None
     if any(c.validity is not None for c in cols):
-        vptrs = (C.c_void_p * len(cols))(*[(c.validity.ptr if c.validity is not None else None) for c in cols])
+        vbits = [_validity_at_zero(c) for c in cols]     # (dbhip_take_chunks takes bare Bitmaps)
+        vptrs = (C.c_void_p * len(cols))(*[(v.ptr if v is not None else None) for v in vbits])
         vb = DeviceBuffer(((n + 63) // 64) * 8 + 8)
         check(lib().dbhip_take_chunks(vptrs, len(cols), 0, C.c_void_p(dp.ptr), C.c_int64(n), C.c_void_p(vb.ptr), None))
     return Column(c0.dtype, n, out, vb, c0.precision, c0.scale, buffers=c0.buffers, keep=tuple(cols))
@@ -1174,9 +1210,9 @@ def _filter_bits(pred, n):
     """The Bitmap a pushed-down predicate hands to the aggregate: a NULL predicate row is dropped like FALSE (the reference's
     filter treats NULL as false, filter_executor.rs), so a nullable Boolean column contributes data AND validity."""
     if pred.validity is None:
-        return pred.data
+        return pred.bits()
     out = DeviceBuffer(((n + 63) // 64) * 8 + 8)
-    check(lib().dbhip_bitmap_binary(0, C.c_void_p(pred.data.ptr), C.c_void_p(pred.validity.ptr), C.c_int64(n), C.c_void_p(out.ptr), None))
+    check(lib().dbhip_bitmap_binary(0, C.c_void_p(pred.bits().ptr), C.c_void_p(_validity_at_zero(pred).ptr), C.c_int64(n), C.c_void_p(out.ptr), None))
     return out
 
 
@@ -1597,7 +1633,8 @@ class HashJoin:
 
     def probe_mark(self, keys_col):
         """-> bool[n]: probe row has a build match (semi / anti / left-outer joins)."""
-        v = C.c_void_p(keys_col.validity.ptr) if keys_col.validity is not None else None
+        vb = _validity_at_zero(keys_col)     # (dbhip_join_* take a bare Bitmap)
+        v = C.c_void_p(vb.ptr) if vb is not None else None
         n = keys_col.n
         bm = DeviceBuffer((max(n, 1) + 7) // 8 + 64)
         total = C.c_uint64()
@@ -1608,7 +1645,8 @@ class HashJoin:
 
     def add_block(self, keys_col):
         """Join::add_block: one build chunk (u64 key column, optional validity)."""
-        v = C.c_void_p(keys_col.validity.ptr) if keys_col.validity is not None else None
+        vb = _validity_at_zero(keys_col)     # (dbhip_join_* take a bare Bitmap)
+        v = C.c_void_p(vb.ptr) if vb is not None else None
         check(lib().dbhip_join_add_build(self.h, C.c_void_p(keys_col.data.ptr), v, C.c_int64(keys_col.n), None))
 
     def final_build(self):
@@ -1616,7 +1654,8 @@ class HashJoin:
 
     def probe_block(self, keys_col):
         """-> (probe_idx u32[], build_row u32[]) sorted by (probe_idx, build_row)."""
-        v = C.c_void_p(keys_col.validity.ptr) if keys_col.validity is not None else None
+        vb = _validity_at_zero(keys_col)     # (dbhip_join_* take a bare Bitmap)
+        v = C.c_void_p(vb.ptr) if vb is not None else None
         total = C.c_uint64()
         check(lib().dbhip_join_probe_count(self.h, C.c_void_p(keys_col.data.ptr), v, C.c_int64(keys_col.n), C.byref(total), None))
         m = total.value
@@ -1629,7 +1668,8 @@ class HashJoin:
 
     def probe_block_device(self, keys_col):
         """Join::probe_block keeping the pair lists in HBM -> (probe_idx DeviceBuffer, build_row DeviceBuffer, n_pairs)."""
-        v = C.c_void_p(keys_col.validity.ptr) if keys_col.validity is not None else None
+        vb = _validity_at_zero(keys_col)     # (dbhip_join_* take a bare Bitmap)
+        v = C.c_void_p(vb.ptr) if vb is not None else None
         total = C.c_uint64()
         check(lib().dbhip_join_probe_count(self.h, C.c_void_p(keys_col.data.ptr), v, C.c_int64(keys_col.n), C.byref(total), None))
         m = total.value
@@ -1697,7 +1737,7 @@ class HashJoin:
             data = DeviceBuffer(max(rows, 1) * es + 64)
             valid = DeviceBuffer(((max(rows, 1) + 63) // 64) * 8 + 8)
             sv = C.c_void_p(c.validity.ptr) if c.validity is not None else None
-            check(lib().dbhip_take_outer(C.c_void_p(c.data.ptr), sv, C.c_int64(0), es, C.c_void_p(bidx.ptr), C.c_int64(rows), C.c_void_p(data.ptr),
+            check(lib().dbhip_take_outer(C.c_void_p(c.data.ptr), sv, C.c_int64(c.voff), es, C.c_void_p(bidx.ptr), C.c_int64(rows), C.c_void_p(data.ptr),
                                          C.c_void_p(valid.ptr), None))
             out_b.append(Column(c.dtype, rows, data, valid, c.precision, c.scale, buffers=c.buffers, keep=(c,)))
         return [take(c, pidx, rows) for c in probe_cols], out_b, rows
@@ -1715,7 +1755,8 @@ class HashJoin:
         if conjunct is not None:
             return self._join_conjunct(kind, probe_keys, probe_cols, build_cols, conjunct)
         n = probe_keys.n
-        v = C.c_void_p(probe_keys.validity.ptr) if probe_keys.validity is not None else None
+        vb = _validity_at_zero(probe_keys)
+        v = C.c_void_p(vb.ptr) if vb is not None else None
         if kind in ("left_semi", "left_anti", "left"):
             words = (max(n, 1) + 63) // 64
             bm = DeviceBuffer(words * 8 + 64)
@@ -1892,7 +1933,7 @@ def concat_columns(cols):
     rows = (C.c_int64 * len(cols))(*[c.n for c in cols])
     boffs = (C.c_int64 * len(cols))(*[c.boff for c in cols])
     got = C.c_int32(0)
-    check(lib().dbhip_concat_columns(_cols(cols), rows, boffs, len(cols), C.c_void_p(out.ptr), C.c_void_p(vb.ptr if vb is not None else None),
+    check(lib().dbhip_concat_columns(_cols(cols, raw_bool=True), rows, boffs, len(cols), C.c_void_p(out.ptr), C.c_void_p(vb.ptr if vb is not None else None),
                                      C.c_void_p(bufs.ptr if bufs is not None else None), C.byref(got), None))
     assert got.value == nbuf
     check(lib().dbhip_stream_sync(None))
