@@ -133,6 +133,11 @@ pub const DBHIP_IN_NEGATE: i32 = 1;
 pub const DBHIP_IN_PATH_BITS: i32 = 0;   // dbhip_inlist_path_t
 pub const DBHIP_IN_PATH_COMPARE: i32 = 1;   // dbhip_inlist_path_t
 pub const DBHIP_IN_PATH_TABLE: i32 = 2;   // dbhip_inlist_path_t
+pub const DBHIP_REGEX_CASE_INSENSITIVE: i32 = 1;
+pub const DBHIP_REGEX_DOT_NL: i32 = 2;
+pub const DBHIP_REGEX_UNIT_BYTE: i32 = 4;
+pub const DBHIP_REGEX_FULL_MATCH: i32 = 8;
+pub const DBHIP_REGEX_NEGATE: i32 = 1;
 pub const DBHIP_VEC_COSINE: i32 = 0;   // dbhip_vec_metric
 pub const DBHIP_VEC_L2: i32 = 1;   // dbhip_vec_metric
 pub const DBHIP_VEC_DOT: i32 = 2;   // dbhip_vec_metric
@@ -144,6 +149,9 @@ pub const DBHIP_IN_MAX_ITEMS: i32 = 1024;
 pub const DBHIP_IN_MAX_ITEM_BYTES: i32 = 255;
 pub const DBHIP_IN_MAX_LONG_BYTES: i32 = 16384;
 pub const DBHIP_STR_PARSE_MAX_BYTES: i32 = 256;
+pub const DBHIP_REGEX_MAX_PATTERN: i32 = 1024;
+pub const DBHIP_REGEX_MAX_STATES: i32 = 4096;
+pub const DBHIP_REGEX_MAX_TABLE_BYTES: i32 = 32768;
 
 #[repr(C)]
 pub struct dbhip_groupby { _private: [u8; 0] }
@@ -153,6 +161,8 @@ pub struct dbhip_join { _private: [u8; 0] }
 pub struct dbhip_join_binary { _private: [u8; 0] }
 #[repr(C)]
 pub struct dbhip_inlist { _private: [u8; 0] }
+#[repr(C)]
+pub struct dbhip_regex { _private: [u8; 0] }
 #[repr(C)]
 pub struct dbhip_vec_index { _private: [u8; 0] }
 #[repr(C)]
@@ -403,6 +413,10 @@ extern "C" {
     pub fn dbhip_str_parse(src: *const dbhip_col, dst_type: i32, dst_precision: u8, dst_scale: u8, is_try: i32, rounding_mode: i32, offset_s: i32, n: i64, out: *mut c_void, bitmap: *mut u8, err_count_dev: *mut u64, declined_count_dev: *mut u64, stream: *mut c_void) -> i32;
     pub fn dbhip_str_format_bytes(src: *const dbhip_col, offset_s: i32, n: i64, out_bytes_host: *mut u64, stream: *mut c_void) -> i32;
     pub fn dbhip_str_format(src: *const dbhip_col, offset_s: i32, n: i64, out_views: *mut c_void, out_data: *mut u8, out_data_bytes: u64, err_count_dev: *mut u64, stream: *mut c_void) -> i32;
+    pub fn dbhip_regex_check(pattern_host: *const u8, pattern_len: i32, flags: i32, out_info_host: *mut i32) -> i32;
+    pub fn dbhip_regex_create(pattern_host: *const u8, pattern_len: i32, flags: i32, out_host: *mut *mut dbhip_regex) -> i32;
+    pub fn dbhip_regex_eval(r: *const dbhip_regex, col: *const dbhip_col, flags: i32, n: i64, out_bitmap: *mut u8, out_declined: *mut u8, declined_count_dev: *mut u64, stream: *mut c_void) -> i32;
+    pub fn dbhip_regex_destroy(r: *mut dbhip_regex) -> i32;
     pub fn dbhip_vec_distance_rows(metric: i32, elem_type: i32, lhs: *const c_void, lhs_is_scalar: i32, rhs: *const c_void, rhs_is_scalar: i32, n: i64, dim: i32, out: *mut c_void, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_distance(metric: i32, base: *const f32, n: i64, dim: i32, queries: *const f32, nq: i32, out: *mut f32, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_topk(metric: i32, base: *const f32, n: i64, dim: i32, queries: *const f32, nq: i32, k: i32, out_idx: *mut u32, out_dist: *mut f32, stream: *mut c_void) -> i32;

@@ -124,6 +124,11 @@ IN_NEGATE = 1
 IN_PATH_BITS, IN_PATH_COMPARE, IN_PATH_TABLE = range(3)
 IN_MAX_ITEMS, IN_MAX_ITEM_BYTES, IN_MAX_LONG_BYTES = 1024, 255, 16384
 
+# the create flags of dbhip_regex_check / dbhip_regex_create, the flag of dbhip_regex_eval and the limits of the group
+REGEX_CASE_INSENSITIVE, REGEX_DOT_NL, REGEX_UNIT_BYTE, REGEX_FULL_MATCH = 1, 2, 4, 8
+REGEX_NEGATE = 1
+REGEX_MAX_PATTERN, REGEX_MAX_STATES, REGEX_MAX_TABLE_BYTES = 1024, 4096, 32768
+
 # DBHIP_STR_PARSE_MAX_BYTES: dbhip_str_parse declines a longer value unread
 STR_PARSE_MAX_BYTES = 256
 
@@ -154,7 +159,7 @@ SYMBOLS = [
     "dbhip_join_destroy", "dbhip_join_mark_build", "dbhip_join_build_matched", "dbhip_sort_perm", "dbhip_merge_sorted_perm", "dbhip_sort_bound_partition",
     "dbhip_window_bounds", "dbhip_window_rank", "dbhip_window_shift", "dbhip_window_value", "dbhip_window_aggregate",
     "dbhip_like_kind", "dbhip_like", "dbhip_str_match", "dbhip_dt_part_type", "dbhip_dt_part", "dbhip_dt_trunc", "dbhip_dt_add", "dbhip_dt_diff", "dbhip_str_length", "dbhip_str_slice", "dbhip_str_build_bytes", "dbhip_str_build",
-    "dbhip_inlist_create", "dbhip_inlist_path", "dbhip_inlist_eval", "dbhip_inlist_destroy", "dbhip_str_parse", "dbhip_str_format_bytes", "dbhip_str_format", "dbhip_bitmap_set_indices", "dbhip_siphash64", "dbhip_scatter_indices", "dbhip_scatter_block", "dbhip_vec_distance", "dbhip_vec_distance_rows", "dbhip_vec_topk", "dbhip_score_u8",
+    "dbhip_inlist_create", "dbhip_inlist_path", "dbhip_inlist_eval", "dbhip_inlist_destroy", "dbhip_str_parse", "dbhip_str_format_bytes", "dbhip_str_format", "dbhip_regex_check", "dbhip_regex_create", "dbhip_regex_eval", "dbhip_regex_destroy", "dbhip_bitmap_set_indices", "dbhip_siphash64", "dbhip_scatter_indices", "dbhip_scatter_block", "dbhip_vec_distance", "dbhip_vec_distance_rows", "dbhip_vec_topk", "dbhip_score_u8",
     "dbhip_vec_topk_merge", "dbhip_vec_index_build", "dbhip_vec_index_search", "dbhip_vec_index_destroy",
     "dbhip_comm_unique_id", "dbhip_comm_create", "dbhip_comm_destroy", "dbhip_comm_abort", "dbhip_comm_allgather", "dbhip_comm_alltoall",
     "dbhip_comm_allreduce_sum_u64", "dbhip_groupby_exchange_allgather", "dbhip_groupby_exchange_alltoall", "dbhip_kmeans", "dbhip_vec_kernel_f32", "dbhip_hnsw_build", "dbhip_hnsw_build_sequential", "dbhip_hnsw_from_graph", "dbhip_hnsw_open", "dbhip_hnsw_export_graph", "dbhip_hnsw_search", "dbhip_hnsw_scores",
@@ -209,6 +214,12 @@ def load_library():
     L.dbhip_inlist_path.argtypes = [C.c_void_p]
     L.dbhip_inlist_eval.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.dbhip_inlist_destroy.argtypes = [C.c_void_p]
+    # the regular-expression group: (pattern, len, flags, out_info[4]) / (pattern, len, flags, out) / (handle, col, flags, n, out_bitmap,
+    # out_declined, declined_count, stream) / (handle)
+    L.dbhip_regex_check.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    L.dbhip_regex_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    L.dbhip_regex_eval.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.dbhip_regex_destroy.argtypes = [C.c_void_p]
     # the String cast group: (src, dst_type, precision, scale, is_try, rounding_mode, offset_s, n, out, bitmap, err_count, declined_count,
     # stream) / (src, offset_s, n, out_bytes_host, stream) / (src, offset_s, n, out_views, out_data, out_data_bytes, err_count, stream)
     L.dbhip_str_parse.argtypes = [C.c_void_p, C.c_int32, C.c_uint8, C.c_uint8, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,

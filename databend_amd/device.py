@@ -637,6 +637,61 @@ def in_list(col, inlist, negate=False, n=None, want_validity=False, stream=None)
     return _match_result(col, n, out)
 
 
+class Regex:
+    """A prepared constant pattern for `x REGEXP p` / regexp_like(x, p) (dbhip_regex_create): the pattern is compiled to a byte-class DFA
+    on the host and its tables are copied to the device once. `.info` is (DFA states, byte classes, table bytes, needs ASCII rows).
+    Raises DbhipError (ERR_UNSUPPORTED) for a pattern outside the grammar or beyond the limits: keep the CPU closure then."""
+
+    def __init__(self, pattern, case_insensitive=False, dot_nl=False, unit_byte=False, full_match=False):
+        _ensure()
+        self.flags = ((L.REGEX_CASE_INSENSITIVE if case_insensitive else 0) | (L.REGEX_DOT_NL if dot_nl else 0) |
+                      (L.REGEX_UNIT_BYTE if unit_byte else 0) | (L.REGEX_FULL_MATCH if full_match else 0))
+        self.handle = None
+        buf, ln = _host_bytes(pattern)
+        info = (C.c_int32 * 4)()
+        check(lib().dbhip_regex_check(buf, C.c_int32(ln), C.c_int32(self.flags), info))
+        self.info = tuple(int(x) for x in info)
+        h = C.c_void_p()
+        check(lib().dbhip_regex_create(buf, C.c_int32(ln), C.c_int32(self.flags), C.byref(h)))
+        self.handle = h.value
+
+    @property
+    def needs_ascii(self):
+        return bool(self.info[3])
+
+    def destroy(self):
+        if getattr(self, "handle", None):
+            lib().dbhip_regex_destroy(C.c_void_p(self.handle))
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def regex_match(col, regex, negate=False, n=None, want_declined=False, stream=None):
+    """col REGEXP regex (NOT with negate) -> (Boolean Column, declined). Like like(), the Column keeps col.validity and its values alone
+    are the filter: the bit under a NULL row and under a declined row is 0 either way. `declined` is the number of rows the device did
+    not decide (a pattern that needs ASCII rows met a byte above 7F): when it is not zero the caller keeps the CPU closure for the
+    block, as with parse_strings. With want_declined the Column carries the declined rows' Bitmap as res.declined (a DeviceBuffer).
+    `stream` is the C call's stream argument (default: the library stream); it is drained here, to read the count."""
+    n, out = _match_out(col, n)
+    dout = DeviceBuffer(((n + 63) // 64) * 8 + 8) if want_declined else None
+    count = DeviceBuffer(8).zero()
+    if stream is not None:
+        check(lib().dbhip_stream_sync(None))     # the counter is zeroed on the library stream
+    cc = col.c()
+    check(lib().dbhip_regex_eval(C.c_void_p(regex.handle), C.byref(cc), C.c_int32(L.REGEX_NEGATE if negate else 0), C.c_int64(n), C.c_void_p(out.ptr),
+                                 C.c_void_p(dout.ptr) if dout is not None else None, C.c_void_p(count.ptr), stream))
+    if stream is not None:
+        check(lib().dbhip_stream_sync(stream))
+    res = _match_result(col, n, out)
+    res.declined = dout
+    return res, int(count.to_numpy(np.uint64, 1)[0])
+
+
 def str_length(col, unit_byte=False, n=None):
     """char_length(col) in UTF-8 units (length(col) in bytes with unit_byte) -> UInt64 Column with the source's validity; 0 under NULL"""
     n = col.n if n is None else n

@@ -878,8 +878,8 @@ int32_t dbhip_window_aggregate(const dbhip_window_rows* rows, const dbhip_agg_de
  * between the launches. Values longer than DBHIP_LIKE_LONG_BYTES that need a search (CONTAINS, SEGMENTS) are handed from the
  * lane-per-row pass to a wave-per-row pass through a row list in scratch (4 bytes per row of the call); the second pass reads the
  * list's length on the device.
- * Out of scope (DBHIP_ERR_UNSUPPORTED or not expressible): a pattern that is a column, ILIKE and collations, REGEXP / RLIKE, a
- * selection-vector form, patterns beyond the limits. */
+ * Out of scope (DBHIP_ERR_UNSUPPORTED or not expressible): a pattern that is a column, ILIKE and collations, a selection-vector
+ * form, patterns beyond the limits. REGEXP / RLIKE is group a25. */
 typedef enum { DBHIP_LIKE_EQUALS = 0, DBHIP_LIKE_PREFIX = 1, DBHIP_LIKE_SUFFIX = 2, DBHIP_LIKE_CONTAINS = 3,
                DBHIP_LIKE_SEGMENTS = 4 } dbhip_like_kind_t;
 enum { DBHIP_LIKE_NEGATE = 1,      /* NOT LIKE: the bit of every non-NULL row is inverted */
@@ -1180,6 +1180,87 @@ int32_t dbhip_str_parse(const dbhip_col* src, int32_t dst_type, uint8_t dst_prec
 int32_t dbhip_str_format_bytes(const dbhip_col* src, int32_t offset_s, int64_t n, uint64_t* out_bytes_host, void* stream);
 int32_t dbhip_str_format(const dbhip_col* src, int32_t offset_s, int64_t n, void* out_views, uint8_t* out_data,
                          uint64_t out_data_bytes, uint64_t* err_count_dev, void* stream);
+/* jit-embed: resume */
+
+/* jit-embed: skip (as a19: the run-time compiled kernels never see this group; the limits and flags the compiler uses are restated in csrc/regex_compile.h) */
+/* ---- a25: regular-expression predicates: x REGEXP p, x RLIKE p, regexp_like(x, p[, match_type]) ----------
+ * Replaces the CPU closure for a CONSTANT pattern (INTEGRATION.md §20 maps the names and the flags) with a prepared, device-resident
+ * DFA and ONE launch per block. The reference's source is not at hand, so this comment is the definition; csrc/regex_compile.h
+ * compiles the pattern and csrc/dev_regex.h walks a value, both once, for the library and for the host checker
+ * (tests/regex_host_check.cpp).
+ *
+ * Result. The bit of a row is 1 iff the pattern matches SOMEWHERE in the value; with DBHIP_REGEX_FULL_MATCH the whole value must
+ * match (exactly as if the pattern were written ^(?:p)$). Only membership is asked, so greedy versus lazy and leftmost-first versus
+ * longest cannot matter: a DFA is exact. The empty pattern matches every value.
+ *
+ * Grammar. Anything outside it is DBHIP_ERR_UNSUPPORTED from dbhip_regex_check and dbhip_regex_create, before any device call: the
+ * binding keeps the CPU closure, which also raises where the pattern is an error.
+ *   Structure    concatenation, `|`, groups ( ), (?: ), (?P<name> ) with name an identifier; an empty branch is allowed. Any other
+ *                (? form — inline flags, look-around — is refused, and so are groups nested more than 64 deep.
+ *   Quantifiers  * + ? {m} {m,} {m,n}, each optionally followed by `?` (lazy: the same set of values). m, n <= 1000 and n >= m. A `{`
+ *                outside a class that does not form one of these is refused. A quantifier on ^ or $, at the start of a branch, or
+ *                directly behind another quantifier (the possessive forms) is refused.
+ *   `.`          one unit other than \n; with DBHIP_REGEX_DOT_NL any unit.
+ *   Classes      [...] and [^...]. Items are literal ASCII bytes, ranges a-z (ascending, between single bytes) and the escapes below.
+ *                A `-` is literal first or last; anywhere else it must form a range. `]`, `[`, `\` and `^` must be escaped (`^` except
+ *                as the negation). && -- ~~, POSIX [:name:], any byte >= 0x80, an empty class and \D \W \S inside a class are refused.
+ *   Escapes      \t \n \r \f \v; \xHH with HH <= 7F (above 7F only under DBHIP_REGEX_UNIT_BYTE); `\` followed by an ASCII punctuation
+ *                byte makes that byte a literal; \d = [0-9], \w = [0-9A-Za-z_], \s = [ \t\n\r\f\v], and \D \W \S as their complements,
+ *                taken as one unit. Every other escape is refused: \b \B \A \z \Z \p{..}, \0 and backreferences among them.
+ *   Anchors      ^ and $ match at the start and at the end of the VALUE only; $ does not match before a trailing \n. No multi-line mode.
+ *   Literals     every other ASCII byte is itself (`]` and `}` included). A pattern byte >= 0x80 outside a class must be part of a
+ *                well-formed UTF-8 sequence, and the whole sequence is one atom (é+ repeats both bytes); under DBHIP_REGEX_UNIT_BYTE
+ *                every byte is its own atom. A byte >= 0x80 together with DBHIP_REGEX_CASE_INSENSITIVE is refused.
+ *
+ * Units. Under DBHIP_REGEX_UNIT_BYTE a unit is one byte. Otherwise `.`, negated classes and \D \W \S consume one unit, which is an
+ * ASCII byte that is not excluded, or a byte C0..FF followed by EVERY directly following byte 80..BF: one code point on valid UTF-8,
+ * and still well defined on arbitrary bytes. A run of bytes 80..BF that follows no lead byte matches nothing.
+ *
+ * Declined rows. DBHIP_REGEX_CASE_INSENSITIVE folds A-Z / a-z only, and \d \w \s and their complements are the ASCII sets, where the
+ * reference's engine is Unicode-aware (k also matches U+212A, \d other scripts' digits). A pattern NEEDS ASCII ROWS when it was
+ * compiled with DBHIP_REGEX_CASE_INSENSITIVE or holds one of \d \w \s \D \W \S, inside a class or not. For such a pattern a valid row
+ * whose value holds a byte >= 0x80 ANYWHERE — also behind the position where the match was already decided, so that the answer does
+ * not depend on where an implementation stops walking — is declined: its out_bitmap bit is 0, also under DBHIP_REGEX_NEGATE, its bit
+ * in out_declined is 1, and it is added to *declined_count_dev. out_declined may be NULL; it has the shape of out_bitmap and is all zero
+ * for other patterns. declined_count_dev may be NULL; the call only ever adds to it. A binding keeps the CPU closure for the block
+ * when the count is not zero, as with non_ascii_count_dev in a22 and declined_count_dev in a24.
+ *
+ * Limits, each DBHIP_ERR_UNSUPPORTED, compilation stopping at the first one passed: pattern_len above DBHIP_REGEX_MAX_PATTERN; more
+ * than 4096 NFA positions (states that consume a byte) after expanding the counted repetitions; more than DBHIP_REGEX_MAX_STATES DFA
+ * states; a table (states * byte classes * 2 bytes) beyond DBHIP_REGEX_MAX_TABLE_BYTES. The DFA is not minimised.
+ * DBHIP_ERR_INVALID: NULL pointers (a NULL pattern with pattern_len 0 is the empty pattern), a negative length, unknown flag bits, a
+ * column that is not DBHIP_T_STRING, n > 2^32 - 2.
+ *
+ * dbhip_regex_check is host only and needs no device and no dbhip_init (like dbhip_like_kind): it compiles, and reports in
+ * out_info_host (may be NULL) {DFA states, byte classes, table bytes, 1 if the pattern needs ASCII rows else 0}.
+ * dbhip_regex_create is the PREPARE step, as dbhip_inlist_create: synchronous; the tables are copied into memory the handle owns, so
+ * the caller's pattern is free after the call. The handle is read-only after create and belongs to the device current at create.
+ * dbhip_regex_eval is asynchronous on `stream`; it never drains, allocates or copies from the host, takes no scratch for a column (16
+ * bytes of the (thread, stream) scratch for an is_scalar one) and is safe from several threads and streams on one handle at once.
+ *
+ * Column and output are a20's. `col` must be DBHIP_T_STRING, its views 16-byte aligned; is_scalar is allowed; validity_offset is
+ * honoured. A NULL row is never dereferenced and its bit is 0, also under DBHIP_REGEX_NEGATE. A long view whose buffer index is >=
+ * n_buffers, or whose table entry is NULL, is never dereferenced: its bit is 0 and it is not declined. Value bytes are read only with
+ * naturally aligned 4-byte loads that cover at least one byte of the value: data buffers need no padding. out_bitmap and out_declined
+ * are LSB-first, written as whole 64-bit words (ceil(n/64)*8 bytes, 8-byte aligned, bits past n zero). n = 0 returns DBHIP_OK. A value
+ * is walked by one lane whatever its length, and the walk stops as soon as the answer cannot change (unless the pattern needs ASCII
+ * rows: then the rest is still tested for bytes >= 0x80).
+ *
+ * Out of scope: a pattern that is a column; regexp_replace / regexp_substr / regexp_instr (they need match positions); multi-line
+ * mode, \b, inline flags, Unicode classes and folding; a selection-vector form; an op inside dbhip_expr_eval programs; literal
+ * prefilters; a second pass for long values. */
+typedef struct dbhip_regex dbhip_regex;              /* opaque; read-only after create; belongs to the device current at create */
+enum { DBHIP_REGEX_CASE_INSENSITIVE = 1, DBHIP_REGEX_DOT_NL = 2, DBHIP_REGEX_UNIT_BYTE = 4, DBHIP_REGEX_FULL_MATCH = 8 }; /* create flags */
+enum { DBHIP_REGEX_NEGATE = 1 };                     /* eval flag: the bit of every valid row that is not declined is inverted */
+#define DBHIP_REGEX_MAX_PATTERN      1024            /* bytes */
+#define DBHIP_REGEX_MAX_STATES       4096
+#define DBHIP_REGEX_MAX_TABLE_BYTES 32768            /* states * byte classes * 2 */
+
+int32_t dbhip_regex_check(const uint8_t* pattern_host, int32_t pattern_len, int32_t flags, int32_t* out_info_host /* [4] */);
+int32_t dbhip_regex_create(const uint8_t* pattern_host, int32_t pattern_len, int32_t flags, dbhip_regex** out_host);
+int32_t dbhip_regex_eval(const dbhip_regex* r, const dbhip_col* col, int32_t flags, int64_t n, uint8_t* out_bitmap,
+                         uint8_t* out_declined, uint64_t* declined_count_dev, void* stream);
+int32_t dbhip_regex_destroy(dbhip_regex* r);
 /* jit-embed: resume */
 
 /* ---- a17/a18: vector distance ------------------------------------------------
