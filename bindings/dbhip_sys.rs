@@ -138,6 +138,13 @@ pub const DBHIP_REGEX_DOT_NL: i32 = 2;
 pub const DBHIP_REGEX_UNIT_BYTE: i32 = 4;
 pub const DBHIP_REGEX_FULL_MATCH: i32 = 8;
 pub const DBHIP_REGEX_NEGATE: i32 = 1;
+pub const DBHIP_MATH_ABS: i32 = 0;   // dbhip_math_fn
+pub const DBHIP_MATH_SIGN: i32 = 1;   // dbhip_math_fn
+pub const DBHIP_MATH_CEIL: i32 = 2;   // dbhip_math_fn
+pub const DBHIP_MATH_FLOOR: i32 = 3;   // dbhip_math_fn
+pub const DBHIP_MATH_ROUND: i32 = 4;   // dbhip_math_fn
+pub const DBHIP_MATH_TRUNCATE: i32 = 5;   // dbhip_math_fn
+pub const DBHIP_MATH_SQRT: i32 = 6;   // dbhip_math_fn
 pub const DBHIP_VEC_COSINE: i32 = 0;   // dbhip_vec_metric
 pub const DBHIP_VEC_L2: i32 = 1;   // dbhip_vec_metric
 pub const DBHIP_VEC_DOT: i32 = 2;   // dbhip_vec_metric
@@ -417,6 +424,8 @@ extern "C" {
     pub fn dbhip_regex_create(pattern_host: *const u8, pattern_len: i32, flags: i32, out_host: *mut *mut dbhip_regex) -> i32;
     pub fn dbhip_regex_eval(r: *const dbhip_regex, col: *const dbhip_col, flags: i32, n: i64, out_bitmap: *mut u8, out_declined: *mut u8, declined_count_dev: *mut u64, stream: *mut c_void) -> i32;
     pub fn dbhip_regex_destroy(r: *mut dbhip_regex) -> i32;
+    pub fn dbhip_math_result(r#fn: i32, src_type: i32, src_precision: u8, src_scale: u8, digits: i32, out_type_host: *mut i32, out_precision_host: *mut u8, out_scale_host: *mut u8) -> i32;
+    pub fn dbhip_math(r#fn: i32, src: *const dbhip_col, digits: i32, n: i64, out: *mut c_void, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_distance_rows(metric: i32, elem_type: i32, lhs: *const c_void, lhs_is_scalar: i32, rhs: *const c_void, rhs_is_scalar: i32, n: i64, dim: i32, out: *mut c_void, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_distance(metric: i32, base: *const f32, n: i64, dim: i32, queries: *const f32, nq: i32, out: *mut f32, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_topk(metric: i32, base: *const f32, n: i64, dim: i32, queries: *const f32, nq: i32, k: i32, out_idx: *mut u32, out_dist: *mut f32, stream: *mut c_void) -> i32;

@@ -874,6 +874,53 @@ def _same_validity(col, n, dtype, out, precision=0, scale=0):
     return res
 
 
+def math_result(fn, col, digits=0):
+    """dbhip_math_result: (result type, precision, scale) of L.MATH_* over `col`; raises where the function is not defined"""
+    t, p, s = C.c_int32(), C.c_uint8(), C.c_uint8()
+    check(lib().dbhip_math_result(C.c_int32(fn), C.c_int32(col.dtype), C.c_uint8(col.precision), C.c_uint8(col.scale), C.c_int32(digits),
+                                  C.byref(t), C.byref(p), C.byref(s)))
+    return t.value, p.value, s.value
+
+
+def math_fn(fn, col, digits=0, n=None):
+    """abs / sign / ceil / floor / round / truncate / sqrt (dbhip_math) -> Column of the result type with the result's DecimalSize, the
+    source's validity. digits: the constant second argument of round / truncate."""
+    n = col.n if n is None else n
+    out_t, p, s = math_result(fn, col, digits)
+    out = DeviceBuffer(max(n, 1) * ELEM_SIZE[out_t] + 64)
+    cc = col.c()
+    check(lib().dbhip_math(C.c_int32(fn), C.byref(cc), C.c_int32(digits), C.c_int64(n), C.c_void_p(out.ptr), None))
+    return _same_validity(col, n, out_t, out, p, s)
+
+
+def abs_(col, n=None):
+    return math_fn(L.MATH_ABS, col, 0, n)
+
+
+def sign(col, n=None):
+    return math_fn(L.MATH_SIGN, col, 0, n)
+
+
+def ceil(col, n=None):
+    return math_fn(L.MATH_CEIL, col, 0, n)
+
+
+def floor(col, n=None):
+    return math_fn(L.MATH_FLOOR, col, 0, n)
+
+
+def round_(col, digits=0, n=None):
+    return math_fn(L.MATH_ROUND, col, digits, n)
+
+
+def truncate(col, digits=0, n=None):
+    return math_fn(L.MATH_TRUNCATE, col, digits, n)
+
+
+def sqrt(col, n=None):
+    return math_fn(L.MATH_SQRT, col, 0, n)
+
+
 def dt_part_type(part, src_type):
     """dbhip_dt_part_type: the fixed result type of a part, or -1"""
     return lib().dbhip_dt_part_type(C.c_int32(part), C.c_int32(src_type))

@@ -41,7 +41,7 @@ extern "C" {
 #endif
 
 #define DBHIP_ABI_VERSION 6   /* 6 (round 6): pipelined fused aggregation (dbhip_groupby_set_pipelined / dbhip_groupby_checkpoint), and (backward
-                                 compatible, same version) DELTA_(LENGTH_)BYTE_ARRAY / BYTE_STREAM_SPLIT on the device with dbhip_pq_chunk_take_arena; likewise the Date / Timestamp functions (a21: dbhip_dt_part / _trunc / _add / _diff, DBHIP_EX_DT_PART / DBHIP_EX_DT_TRUNC); 5 (round 5): ZSTD on the device, batched chunk decode (dbhip_pq_chunks_decode_device); 4 (round 4): block scatter / concat, exchange and plan calls, device-mode scan, cancellation, row-wise vector distance */
+                                 compatible, same version) DELTA_(LENGTH_)BYTE_ARRAY / BYTE_STREAM_SPLIT on the device with dbhip_pq_chunk_take_arena; likewise the Date / Timestamp functions (a21: dbhip_dt_part / _trunc / _add / _diff, DBHIP_EX_DT_PART / DBHIP_EX_DT_TRUNC) and the math functions (a26: dbhip_math_result / dbhip_math; 192 functions in all); 5 (round 5): ZSTD on the device, batched chunk decode (dbhip_pq_chunks_decode_device); 4 (round 4): block scatter / concat, exchange and plan calls, device-mode scan, cancellation, row-wise vector distance */
 
 /* ---- status codes ------------------------------------------------------- */
 enum {
@@ -1261,6 +1261,64 @@ int32_t dbhip_regex_create(const uint8_t* pattern_host, int32_t pattern_len, int
 int32_t dbhip_regex_eval(const dbhip_regex* r, const dbhip_col* col, int32_t flags, int64_t n, uint8_t* out_bitmap,
                          uint8_t* out_declined, uint64_t* declined_count_dev, void* stream);
 int32_t dbhip_regex_destroy(dbhip_regex* r);
+/* jit-embed: resume */
+
+/* jit-embed: skip (as a19: the run-time compiled kernels never see this group; the codes the kernels use are restated in csrc/dev_math.h) */
+/* ---- a26: math functions: abs, sign, ceil, floor, round, truncate, sqrt ----------
+ * Replaces the CPU closures of the unary numeric functions and of round / truncate with a CONSTANT second argument (INTEGRATION.md
+ * §21 maps the names) with ONE launch per block. The reference's source is not at hand, so this comment is the definition;
+ * csrc/dev_math.h states it once in code, for the library and for the host checker (tests/math_host_check.cpp). Every function is
+ * exact: integer arithmetic, or IEEE-754 operations that are correctly rounded on every side, so results are compared bit for bit.
+ * Where the reference registers another result type the binding widens with dbhip_cast.
+ *
+ * Number sources (I8 .. U64, F32, F64):
+ *   ABS       signed iN -> uN of the same width: v < 0 ? 0 - (uN)v : v, so abs of the minimum is exact. F32 -> F32 and F64 -> F64: the
+ *             sign bit cleared, so -0.0 -> +0.0 and a NaN keeps its payload. An unsigned source is the identity: DBHIP_ERR_INVALID
+ *             (the binding passes the column through).
+ *   SIGN      -> I8: v > 0 ? 1 : v < 0 ? -1 : 0. NaN, +0.0 and -0.0 give 0.
+ *   CEIL, FLOOR -> F64: x = (double)v (I64 / U64 round to nearest even), then ceil(x) / floor(x). +-0, +-Inf and NaN pass through;
+ *             ceil(-0.5) = -0.0.
+ *   ROUND, TRUNCATE -> F64: x = (double)v; d = clamp(digits, -30, 30); R = round (half away from zero) for ROUND, trunc for TRUNCATE;
+ *             d == 0: R(x);  d > 0: R(x * P[d]) / P[d];  d < 0: R(x / P[-d]) * P[-d], the operations in exactly this order and none
+ *             fused. P[k] is the f64 NEAREST to 10^k (the decimal literal 1e<k>, not pow and not a running product). Overflow to
+ *             +-Inf is the result, not an error.
+ *   SQRT      -> F64: sqrt((double)v), correctly rounded. sqrt(-0.0) = -0.0; a negative source gives NaN; it never raises.
+ *   A result that is a NaN is any NaN, except in ABS.
+ *
+ * Decimal sources (DEC64, DEC128; p, s the source's precision and scale, v the stored integer; exact integers, `/` truncates toward
+ * zero). The result has the source's storage class and precision in every case except SIGN:
+ *   ABS       (p, s): v < 0 ? -v : v, wrapping.
+ *   SIGN      -> I8, as for numbers.
+ *   CEIL      (p, 0): v > 0 ? (v + 10^s - 1) / 10^s : v / 10^s.
+ *   FLOOR     (p, 0): v < 0 ? (v - 10^s + 1) / 10^s : v / 10^s.
+ *   ROUND, TRUNCATE (p, clamp(digits, 0, s)): let k = s - digits. k <= 0: the values unchanged. 0 < k <= p: q = (|v| + h) / 10^k with
+ *             h = 10^k / 2 for ROUND and 0 for TRUNCATE; q is multiplied by 10^(-digits) when digits < 0 and given the sign of v.
+ *             k > p: every row is 0.
+ *   Nothing overflows the storage for |v| <= 10^p. A result may have p + 1 digits (round(999 :: Decimal(3,0), -1) = 1000); the
+ *   reference does not check this either, so it is not a row error. A DEC256 source is DBHIP_ERR_UNSUPPORTED for every function:
+ *   the binding keeps the CPU closure. SQRT of a DEC64 / DEC128 is not in the table: DBHIP_ERR_INVALID (cast to Float64 first).
+ *
+ * `digits` is the constant second argument of ROUND / TRUNCATE; the other functions ignore it. A column as second argument is not
+ * offered. The functions never raise, so there is no error bitmap. Validity passes through: the binding reuses the source's Bitmap
+ * (as for dbhip_decimal_neg and a21), and the payload is computed for every row. is_scalar sources are allowed. n = 0 returns
+ * DBHIP_OK before any launch. `out` holds n values of the result type. Sliced columns are accepted: src->data and out need only be
+ * aligned to their element (a DEC128 to 8 bytes); the kernel picks 16-byte or per-element accesses by the two bases.
+ *
+ * dbhip_math_result is host only and needs no device and no dbhip_init: the result type and DecimalSize (precision and scale are 0
+ * for a result that is no decimal) of fn over a source. It is the one place that decides what is defined: anything else — an unknown
+ * fn, ABS of an unsigned type, Bool / String / Date / Timestamp sources, a precision outside 1 .. 18 (DEC64) / 1 .. 38 (DEC128) or a
+ * scale above the precision, NULL output pointers — is DBHIP_ERR_INVALID. dbhip_math asks it before any device call and returns its
+ * status; the stream stays usable after a refusal. dbhip_math is asynchronous on `stream` and takes no scratch.
+ *
+ * Out of scope: the transcendental functions (exp, ln, log*, pow, cbrt, trigonometry: no two libms agree bit for bit, they need a
+ * tolerance contract of their own); a column as `digits`; DEC256; ops inside dbhip_expr_eval programs. */
+typedef enum { DBHIP_MATH_ABS = 0, DBHIP_MATH_SIGN = 1, DBHIP_MATH_CEIL = 2, DBHIP_MATH_FLOOR = 3,
+               DBHIP_MATH_ROUND = 4, DBHIP_MATH_TRUNCATE = 5, DBHIP_MATH_SQRT = 6 } dbhip_math_fn;
+
+/* host only, no device needed: the result type and DecimalSize of fn over a source; DBHIP_OK / _INVALID / _UNSUPPORTED */
+int32_t dbhip_math_result(int32_t fn, int32_t src_type, uint8_t src_precision, uint8_t src_scale, int32_t digits,
+                          int32_t* out_type_host, uint8_t* out_precision_host, uint8_t* out_scale_host);
+int32_t dbhip_math(int32_t fn, const dbhip_col* src, int32_t digits, int64_t n, void* out, void* stream);
 /* jit-embed: resume */
 
 /* ---- a17/a18: vector distance ------------------------------------------------

@@ -11,6 +11,18 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCALARS = {"int8_t": "i8", "int16_t": "i16", "int32_t": "i32", "int64_t": "i64", "uint8_t": "u8", "uint16_t": "u16", "uint32_t": "u32",
            "uint64_t": "u64", "float": "f32", "double": "f64", "size_t": "usize", "char": "c_char", "void": "c_void", "int": "c_int"}
+# strict and reserved keywords of Rust (2015 - 2024 editions): a C field or parameter of such a name is written as a raw identifier
+RUST_KEYWORDS = frozenset("""as break const continue crate else enum extern false fn for if impl in let loop match mod move mut pub ref return
+self Self static struct super trait true type unsafe use where while async await dyn abstract become box do final macro override priv
+typeof unsized virtual yield try gen""".split())
+NOT_RAW = frozenset(["self", "Self", "super", "crate"])          # these cannot be raw identifiers: a trailing underscore instead
+
+
+def rust_ident(name):
+    """a C field or parameter name as a Rust identifier: `fn` -> `r#fn`, `type` -> `r#type`"""
+    if name in NOT_RAW:
+        return name + "_"
+    return "r#" + name if name in RUST_KEYWORDS else name
 
 
 def strip_comments(text):
@@ -124,11 +136,11 @@ def render(header_text):
     out.append("")
     for name, fields in structs:
         out += ["#[repr(C)]", "#[derive(Clone, Copy)]", f"pub struct {name} {{"]
-        out += [f"    pub {'r#type' if fn == 'type' else fn}: {ft}," for fn, ft in fields]
+        out += [f"    pub {rust_ident(fn)}: {ft}," for fn, ft in fields]
         out += ["}", ""]
     out.append('extern "C" {')
     for name, args, ret in funcs:
-        a = ", ".join(f"{'r#type' if an == 'type' else an}: {at}" for an, at in args)
+        a = ", ".join(f"{rust_ident(an)}: {at}" for an, at in args)
         out.append(f"    pub fn {name}({a})" + (f" -> {ret};" if ret else ";"))
     out += ["}", ""]
     return "\n".join(out), [f[0] for f in funcs]
