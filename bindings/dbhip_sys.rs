@@ -145,6 +145,10 @@ pub const DBHIP_MATH_FLOOR: i32 = 3;   // dbhip_math_fn
 pub const DBHIP_MATH_ROUND: i32 = 4;   // dbhip_math_fn
 pub const DBHIP_MATH_TRUNCATE: i32 = 5;   // dbhip_math_fn
 pub const DBHIP_MATH_SQRT: i32 = 6;   // dbhip_math_fn
+pub const DBHIP_BOOL_AND: i32 = 0;   // dbhip_bool_op
+pub const DBHIP_BOOL_OR: i32 = 1;   // dbhip_bool_op
+pub const DBHIP_BOOL_NOT: i32 = 2;   // dbhip_bool_op
+pub const DBHIP_BOOL_XOR: i32 = 3;   // dbhip_bool_op
 pub const DBHIP_VEC_COSINE: i32 = 0;   // dbhip_vec_metric
 pub const DBHIP_VEC_L2: i32 = 1;   // dbhip_vec_metric
 pub const DBHIP_VEC_DOT: i32 = 2;   // dbhip_vec_metric
@@ -159,6 +163,7 @@ pub const DBHIP_STR_PARSE_MAX_BYTES: i32 = 256;
 pub const DBHIP_REGEX_MAX_PATTERN: i32 = 1024;
 pub const DBHIP_REGEX_MAX_STATES: i32 = 4096;
 pub const DBHIP_REGEX_MAX_TABLE_BYTES: i32 = 32768;
+pub const DBHIP_CASE_MAX_CONDS: i32 = 16;
 
 #[repr(C)]
 pub struct dbhip_groupby { _private: [u8; 0] }
@@ -426,6 +431,10 @@ extern "C" {
     pub fn dbhip_regex_destroy(r: *mut dbhip_regex) -> i32;
     pub fn dbhip_math_result(r#fn: i32, src_type: i32, src_precision: u8, src_scale: u8, digits: i32, out_type_host: *mut i32, out_precision_host: *mut u8, out_scale_host: *mut u8) -> i32;
     pub fn dbhip_math(r#fn: i32, src: *const dbhip_col, digits: i32, n: i64, out: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn dbhip_case_check(conds_host: *const dbhip_col, n_conds: i32, values_host: *const dbhip_col, n_values: i32) -> i32;
+    pub fn dbhip_case(conds_host: *const dbhip_col, n_conds: i32, values_host: *const dbhip_col, n: i64, out: *mut c_void, out_validity: *mut u8, out_branch: *mut u8, out_buffers_dev: *mut *const c_void, out_n_buffers_host: *mut i32, stream: *mut c_void) -> i32;
+    pub fn dbhip_coalesce(args_host: *const dbhip_col, n_args: i32, n: i64, out: *mut c_void, out_validity: *mut u8, out_branch: *mut u8, out_buffers_dev: *mut *const c_void, out_n_buffers_host: *mut i32, stream: *mut c_void) -> i32;
+    pub fn dbhip_bool_logic(op: i32, a: *const dbhip_col, b: *const dbhip_col, n: i64, out_values: *mut u8, out_validity: *mut u8, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_distance_rows(metric: i32, elem_type: i32, lhs: *const c_void, lhs_is_scalar: i32, rhs: *const c_void, rhs_is_scalar: i32, n: i64, dim: i32, out: *mut c_void, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_distance(metric: i32, base: *const f32, n: i64, dim: i32, queries: *const f32, nq: i32, out: *mut f32, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_topk(metric: i32, base: *const f32, n: i64, dim: i32, queries: *const f32, nq: i32, k: i32, out_idx: *mut u32, out_dist: *mut f32, stream: *mut c_void) -> i32;

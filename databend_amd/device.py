@@ -921,6 +921,144 @@ def sqrt(col, n=None):
     return math_fn(L.MATH_SQRT, col, 0, n)
 
 
+def null_scalar(dtype, precision=0, scale=0):
+    """the constant NULL of a type: a scalar whose validity bit is 0 and whose data pointer is NULL (the ELSE of a CASE without one)"""
+    return Column(dtype, 1, BorrowedBuffer(0, 0), DeviceBuffer.from_numpy(np.zeros(8, np.uint8)), precision, scale, is_scalar=True)
+
+
+def _rows_of(cols, n):
+    return n if n is not None else max([c.n for c in cols if not c.is_scalar], default=1)
+
+
+def _ptr(buf):
+    return C.c_void_p(buf.ptr) if buf is not None else None
+
+
+def _select(conds, values, n, want_branch, out, out_validity, out_branch):
+    """dbhip_case (conds given) / dbhip_coalesce (conds None) -> Column of the values' type. The result is nullable when a value is;
+    a String result carries the arguments' buffer tables back to back and keeps the sources alive. res.branch (want_branch): a U8
+    Column, the branch index of every row."""
+    conds = list(conds) if conds is not None else None
+    values = list(values)
+    n = _rows_of((conds or []) + values, n)
+    v0 = values[0]
+    t = v0.dtype
+    words = (max(n, 1) + 63) // 64
+    if out is None:
+        out = DeviceBuffer(words * 8 if t == L.T_BOOL else max(n, 1) * ELEM_SIZE.get(t, 32) + 64)
+    if out_validity is None and any(v.validity is not None for v in values):
+        out_validity = DeviceBuffer(words * 8)
+    if out_branch is None and want_branch:
+        out_branch = DeviceBuffer(max(n, 1))
+    nbuf = sum(v.n_buffers for v in values) if t == L.T_STRING else 0
+    table = DeviceBuffer(nbuf * 8) if nbuf else None
+    got = C.c_int32(-1)
+    varr = _cols(values)
+    if conds is not None:
+        check(lib().dbhip_case(_cols(conds) if conds else None, C.c_int32(len(conds)), varr, C.c_int64(n), _ptr(out), _ptr(out_validity), _ptr(out_branch),
+                               _ptr(table), C.byref(got), None))
+    else:
+        check(lib().dbhip_coalesce(varr, C.c_int32(len(values)), C.c_int64(n), _ptr(out), _ptr(out_validity), _ptr(out_branch), _ptr(table),
+                                   C.byref(got), None))
+    assert got.value == nbuf, (got.value, nbuf)
+    res = Column(t, n, out, out_validity, v0.precision, v0.scale, buffers=table, keep=tuple(conds or ()) + tuple(values))
+    res.n_buffers = nbuf
+    res.branch = Column(L.T_U8, n, out_branch) if out_branch is not None else None
+    return res
+
+
+def case_when(conds, values, n=None, want_branch=False, out=None, out_validity=None, out_branch=None):
+    """CASE WHEN conds[0] THEN values[0] ... ELSE values[-1] END / multi_if (dbhip_case): Boolean Columns or scalars, and
+    len(conds) + 1 values of one type; a CASE without ELSE passes null_scalar(type) last. out / out_validity / out_branch: caller's
+    buffers (anything with .ptr) instead of fresh ones."""
+    return _select(conds, values, n, want_branch, out, out_validity, out_branch)
+
+
+def coalesce(*args, n=None, want_branch=False, out=None, out_validity=None, out_branch=None):
+    """coalesce(a, b, ...) (dbhip_coalesce): the first argument that is not NULL; branch len(args) marks the rows that stay NULL"""
+    return _select(None, args, n, want_branch, out, out_validity, out_branch)
+
+
+def if_(cond, then, other, n=None, want_branch=False):
+    return case_when([cond], [then, other], n, want_branch)
+
+
+def ifnull(a, b, n=None):
+    """ifnull / nvl"""
+    return coalesce(a, b, n=n)
+
+
+def bool_logic(op, a, b=None, n=None, out=None, out_validity=None):
+    """Kleene and / or / not / xor over nullable Boolean Columns or scalars (dbhip_bool_logic) -> Boolean Column: its values are the
+    TRUE rows, its validity (when an operand is nullable) the rows that are not NULL"""
+    ops = [a] if b is None else [a, b]
+    n = _rows_of(ops, n)
+    words = (max(n, 1) + 63) // 64
+    out = DeviceBuffer(words * 8) if out is None else out
+    if out_validity is None and any(x.validity is not None for x in ops):
+        out_validity = DeviceBuffer(words * 8)
+    ca = a.c()
+    cb = b.c() if b is not None else None
+    check(lib().dbhip_bool_logic(C.c_int32(op), C.byref(ca), C.byref(cb) if cb is not None else None, C.c_int64(n), _ptr(out), _ptr(out_validity), None))
+    return Column(L.T_BOOL, n, out, out_validity, keep=tuple(ops))
+
+
+def bool_and(a, b, n=None):
+    return bool_logic(L.BOOL_AND, a, b, n)
+
+
+def bool_or(a, b, n=None):
+    return bool_logic(L.BOOL_OR, a, b, n)
+
+
+def bool_not(a, n=None):
+    return bool_logic(L.BOOL_NOT, a, None, n)
+
+
+def bool_xor(a, b, n=None):
+    return bool_logic(L.BOOL_XOR, a, b, n)
+
+
+def _bitmap_op(mode, a, b, n):
+    out = DeviceBuffer(((max(n, 1) + 63) // 64) * 8)
+    check(lib().dbhip_bitmap_binary(mode, C.c_void_p(a.ptr), C.c_void_p(b.ptr), C.c_int64(n), C.c_void_p(out.ptr), None))
+    return out
+
+
+def _validity_bits(col, n):
+    """the validity of a Column as a Bitmap at bit 0 over n rows: a scalar's bit repeated, all ones for a Column without one"""
+    if col.validity is None or col.is_scalar:
+        return DeviceBuffer.from_numpy(pack_bits(np.repeat(col.validity_numpy()[:1] if col.validity is not None else True, n)))
+    return _validity_at_zero(col)
+
+
+def is_not_null(col, n=None):
+    """is_not_null(col): the validity realigned to bit 0, never NULL itself"""
+    n = _rows_of([col], n)
+    return Column(L.T_BOOL, n, _validity_bits(col, n), keep=(col,))
+
+
+def is_null(col, n=None):
+    n = _rows_of([col], n)
+    ones = DeviceBuffer.from_numpy(pack_bits(np.ones(n, dtype=bool)))
+    return Column(L.T_BOOL, n, _bitmap_op(2, ones, _validity_bits(col, n), n), keep=(col,))
+
+
+def nullif(a, b, n=None):
+    """nullif(a, b): a, NULL where a = b. Composed from existing calls: dbhip_cmp(EQ), then the validity va AND NOT (eq AND vb) through
+    dbhip_bitmap_binary; the payload of `a` is reused as it is."""
+    assert not a.is_scalar
+    n = _rows_of([a, b], n)
+    eq = cmp(L.CMP_EQ, a, b, n)
+    hit = eq.bits()
+    if eq.validity is not None:                       # va AND vb: the rows where the comparison means something
+        hit = _bitmap_op(0, hit, _bits_at_zero(eq.validity, eq.voff, n), n)
+    res = Column(a.dtype, n, a.data, _bitmap_op(2, _validity_bits(a, n), hit, n), a.precision, a.scale, buffers=a.buffers, keep=(a, b))
+    res.n_buffers = a.n_buffers
+    res._keep = (a, b) + tuple(a._keep)
+    return res
+
+
 def dt_part_type(part, src_type):
     """dbhip_dt_part_type: the fixed result type of a part, or -1"""
     return lib().dbhip_dt_part_type(C.c_int32(part), C.c_int32(src_type))

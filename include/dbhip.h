@@ -41,7 +41,7 @@ extern "C" {
 #endif
 
 #define DBHIP_ABI_VERSION 6   /* 6 (round 6): pipelined fused aggregation (dbhip_groupby_set_pipelined / dbhip_groupby_checkpoint), and (backward
-                                 compatible, same version) DELTA_(LENGTH_)BYTE_ARRAY / BYTE_STREAM_SPLIT on the device with dbhip_pq_chunk_take_arena; likewise the Date / Timestamp functions (a21: dbhip_dt_part / _trunc / _add / _diff, DBHIP_EX_DT_PART / DBHIP_EX_DT_TRUNC) and the math functions (a26: dbhip_math_result / dbhip_math; 192 functions in all); 5 (round 5): ZSTD on the device, batched chunk decode (dbhip_pq_chunks_decode_device); 4 (round 4): block scatter / concat, exchange and plan calls, device-mode scan, cancellation, row-wise vector distance */
+                                 compatible, same version) DELTA_(LENGTH_)BYTE_ARRAY / BYTE_STREAM_SPLIT on the device with dbhip_pq_chunk_take_arena; likewise the Date / Timestamp functions (a21: dbhip_dt_part / _trunc / _add / _diff, DBHIP_EX_DT_PART / DBHIP_EX_DT_TRUNC), the math functions (a26: dbhip_math_result / dbhip_math) and the conditionals (a27: dbhip_case_check / dbhip_case / dbhip_coalesce / dbhip_bool_logic; 196 functions in all); 5 (round 5): ZSTD on the device, batched chunk decode (dbhip_pq_chunks_decode_device); 4 (round 4): block scatter / concat, exchange and plan calls, device-mode scan, cancellation, row-wise vector distance */
 
 /* ---- status codes ------------------------------------------------------- */
 enum {
@@ -1319,6 +1319,82 @@ typedef enum { DBHIP_MATH_ABS = 0, DBHIP_MATH_SIGN = 1, DBHIP_MATH_CEIL = 2, DBH
 int32_t dbhip_math_result(int32_t fn, int32_t src_type, uint8_t src_precision, uint8_t src_scale, int32_t digits,
                           int32_t* out_type_host, uint8_t* out_precision_host, uint8_t* out_scale_host);
 int32_t dbhip_math(int32_t fn, const dbhip_col* src, int32_t digits, int64_t n, void* out, void* stream);
+/* jit-embed: resume */
+
+/* jit-embed: skip (as a19: the run-time compiled kernels never see this group; the codes the kernels use are restated in csrc/dev_cond.h) */
+/* ---- a27: conditionals: CASE / if, coalesce, three-valued AND / OR / NOT / XOR ----------
+ * Replaces the CPU closures of if / multi_if / CASE, coalesce / ifnull / nvl and of and / or / not / xor over nullable operands
+ * (INTEGRATION.md §22 maps the names, nullif, is_null and is_not_null included) with ONE launch per call. The reference's source is not
+ * at hand, so this comment is the definition; csrc/dev_cond.h states it once in code, for the library and for the host checker
+ * (tests/cond_host_check.cpp). A conditional is a select: the kernel moves elements and never interprets them, so all seventeen
+ * physical types are accepted, String and Decimal256 included, and every result is compared bit for bit.
+ *
+ * Choice.
+ *   dbhip_case      row i takes branch k, the smallest k for which condition k is TRUE at i. TRUE means: the validity bit is set (or
+ *                   the condition has no validity) AND the value bit is set. A NULL condition is not TRUE, whatever its payload bit
+ *                   says. If no condition is TRUE the row takes branch n_conds, which is ELSE: values_host holds n_conds + 1
+ *                   entries. CASE without ELSE passes a NULL scalar as the last value.
+ *   dbhip_coalesce  row i takes the first argument that is valid at i, and branch n_args (NULL) if none is. ifnull / nvl are the
+ *                   two-argument form.
+ *
+ * Result. out[i] is the chosen branch's value at i (the one value of a scalar), and the result is valid iff that value is valid. A row
+ * whose result is NULL holds zero: the value 0, the all-zero view, or the bit 0. A scalar whose validity bit is 0 is never
+ * dereferenced, and its `data` may be NULL. out_validity may be NULL; otherwise it is LSB-first, written as whole 64-bit words:
+ * ceil(n / 64) * 8 bytes, 8-byte aligned, bits past n zero. out_branch may be NULL; otherwise it is n bytes, the branch index of each
+ * row. The binding uses it to keep the reference's lazy branches honest: a row error raised by branch k's expression counts only
+ * where out_branch == k, which it gets as dbhip_cmp(EQ, out_branch as a U8 column, scalar k) followed by dbhip_bitmap_binary on the
+ * branch's err_bitmap (INTEGRATION.md §22 spells the recipe out).
+ *
+ * Types. Conditions are DBHIP_T_BOOL columns or scalars: their values a Bitmap at bit 0, as everywhere, their validity read from
+ * validity_offset. All values have one dbhip_type; decimals also share one precision and one scale (the planner casts). Elements of
+ * 1 / 2 / 4 / 8 / 16 / 32 bytes are moved as they are. BOOL values are Bitmaps at bit 0, and the BOOL result is a Bitmap in the
+ * out_validity form.
+ *
+ * Strings. No value byte is read or copied. The result column's buffer table is the arguments' tables back to back in argument order,
+ * scalars' tables included: it is written to out_buffers_dev, and *out_n_buffers_host receives the sum, exactly as in
+ * dbhip_concat_columns. A long view is copied with its buffer index rebased by the entries in front of its argument; an inline view
+ * is copied as it is. Both pointers may be NULL when every n_buffers is 0, and for other types.
+ *
+ * Columns. Data need only be aligned to the element, a Decimal128 / 256 to 8 bytes; views are 16-byte aligned. Sliced columns are
+ * accepted, as in dbhip_math: the kernel picks 16-byte or per-element accesses by each base.
+ *
+ * Status. n = 0 returns DBHIP_OK before any launch. dbhip_case and dbhip_coalesce ask dbhip_case_check first and return its status;
+ * the stream stays usable after a refusal. dbhip_case_check is host only and needs no device and no dbhip_init: it reads the
+ * descriptors' type / precision / scale / is_scalar / n_buffers and no pointer; with conds_host = NULL and n_conds = 0 it checks a
+ * coalesce of n_values arguments. DBHIP_ERR_INVALID: a NULL array, n_conds < 1 for a case, n_values != n_conds + 1, n_args < 1, a
+ * condition that is not BOOL, values of different types or DecimalSizes, an unknown type (and, from the calls themselves, NULL or
+ * misaligned data). DBHIP_ERR_UNSUPPORTED: more than DBHIP_CASE_MAX_CONDS conditions, or more than DBHIP_CASE_MAX_CONDS + 1 coalesce
+ * arguments: the binding nests the call or keeps the CPU closure.
+ *
+ * dbhip_bool_logic is Kleene logic over nullable Boolean columns or scalars. With va, vb the validities (all ones when absent) and a, b
+ * the value bits:
+ *   AND   valid = va&vb | va&~a | vb&~b     true = va&a&vb&b
+ *   OR    valid = va&vb | va&a | vb&b       true = va&a | vb&b
+ *   NOT   valid = va                        true = va&~a              (b is NULL)
+ *   XOR   valid = va&vb                     true = valid & (a^b)
+ * out_values is the `true` Bitmap: 0 where the result is FALSE or NULL. Both outputs are whole 64-bit words, 8-byte aligned, with the
+ * bits past n zero; out_validity may be NULL. This is the and / or / not / xor of the reference over nullable operands, anywhere;
+ * and_filters / or_filters keep DBHIP_EX_IS_TRUE.
+ *
+ * Calls. Every call is asynchronous on `stream`: ONE launch, no scratch, no drain, no upload. The String table costs at most a
+ * device-to-device copy per argument on the same stream. The up to 33 column descriptors travel by value in the kernel arguments
+ * (about 1 KiB).
+ *
+ * Out of scope: ops inside dbhip_expr_eval and fused-aggregation programs (DBHIP_EX_IF stays as it is); a selection-vector form; branch
+ * values of different types; the C++ host mirror and the Rust shim (which do not wrap a21 - a26 either); nullif as a call of its own
+ * (it is dbhip_cmp + dbhip_bitmap_binary over the first argument's payload). */
+#define DBHIP_CASE_MAX_CONDS 16
+typedef enum { DBHIP_BOOL_AND = 0, DBHIP_BOOL_OR = 1, DBHIP_BOOL_NOT = 2, DBHIP_BOOL_XOR = 3 } dbhip_bool_op;
+
+/* host only, no device and no dbhip_init: reads the descriptors' type / precision / scale / is_scalar / n_buffers, no pointer */
+int32_t dbhip_case_check(const dbhip_col* conds_host, int32_t n_conds, const dbhip_col* values_host, int32_t n_values);
+int32_t dbhip_case(const dbhip_col* conds_host, int32_t n_conds, const dbhip_col* values_host /* n_conds + 1, the last is ELSE */,
+                   int64_t n, void* out, uint8_t* out_validity, uint8_t* out_branch,
+                   const void** out_buffers_dev, int32_t* out_n_buffers_host, void* stream);
+int32_t dbhip_coalesce(const dbhip_col* args_host, int32_t n_args, int64_t n, void* out, uint8_t* out_validity, uint8_t* out_branch,
+                       const void** out_buffers_dev, int32_t* out_n_buffers_host, void* stream);
+int32_t dbhip_bool_logic(int32_t op, const dbhip_col* a, const dbhip_col* b /* NULL for NOT */, int64_t n,
+                         uint8_t* out_values, uint8_t* out_validity, void* stream);
 /* jit-embed: resume */
 
 /* ---- a17/a18: vector distance ------------------------------------------------
