@@ -125,8 +125,8 @@ def test_fused_decimal_program_row_errors(gpu, oracle):
 
 
 DIV_CASES = [
-    # (op, a: (type, precision, scale, lo, hi), b: likewise) — every branch of dec_row that divides
-    (T.OP_MULTIPLY, (T.T_DEC64, 9, 6, -10**8, 10**8), (T.T_DEC64, 9, 6, -10**8, 10**8)),          # T = i64, rounding multiply, checked range
+    # (op, a: (type, precision, scale, lo, hi), b: likewise) — branches of dec_row that divide (their edges: test_gpu_decimal_edges.py)
+    (T.OP_MULTIPLY, (T.T_DEC64, 9, 6, -10**8, 10**8), (T.T_DEC64, 9, 6, -10**8, 10**8)),          # T = i64 at precision 18, scale shift 0: rounds nothing, checks nothing
     (T.OP_MULTIPLY, (T.T_DEC64, 15, 8, -10**14, 10**14), (T.T_DEC64, 15, 8, -10**14, 10**14)),    # T = i128, no overflow check
     (T.OP_MULTIPLY, (T.T_DEC128, 38, 10, -10**30, 10**30), (T.T_DEC64, 18, 10, -10**17, 10**17)),  # T = i128 at precision 38: 256-bit product, may overflow
     (T.OP_DIVIDE, (T.T_DEC64, 9, 2, -10**8, 10**8), (T.T_DEC64, 9, 4, -300, 300)),                # divide, zero divisors raise
