@@ -15,7 +15,7 @@
 // row holds zero without a second pass. The validity word of 64 rows is computed whole, from words, by every lane that owns rows of it;
 // the lane that owns its first row stores it. No word is written by two lanes, nothing is atomic, and nothing needs a ballot to be
 // assembled. out_branch is merged the same way, one byte per row.
-// Sliced columns: a wave-uniform test of each base picks 16-byte or per-element accesses (as k_math.hip); the rows of the last, partial
+// Sliced columns: a wave-uniform test of each base picks 16-byte or per-element accesses (as dev_map.h); the rows of the last, partial
 // run go per element. A scalar is read where a lane took it, one address for the wave.
 // cond_bits_kernel (BOOL values) and bool_logic_kernel are word-wise: a lane owns one 64-row word of the outputs and builds it from
 // input words fetched at their bit offsets. No LDS, no scratch memory, no atomics anywhere.

@@ -4,6 +4,8 @@
 // memory side. Every kernel is a map whose lanes each own a run of CONSECUTIVE rows sized so that the narrower of input and output
 // moves as whole 16-byte vectors: a U8 part takes 16 rows per lane (4 or 8 dwordx4 loads, one dwordx4 store), U16 8, U32 / Date 4,
 // 64-bit results 2. The last n mod rows-per-lane rows are done one per lane by the first workgroup. A scalar input is read once per lane.
+// The loop of the one-input kernels and every memory access are dev_map.h's; the entry points insist on 16-byte bases, so the kernels
+// pass std::true_type() and have its 16-byte form alone.
 // Validity is not touched: it passes through (the binding reuses the source's bitmap); the add kernel reads a row's validity bits only
 // when that row fails, to keep a NULL row from raising.
 // Time zone: a fixed offset travels as a kernel argument and those instantiations use no LDS. A transition table (dbhip_dt_part only)
@@ -14,6 +16,7 @@
 
 #include "dev_common.h"
 #include "dev_datetime.h"
+#include "dev_map.h"
 #include "runtime.h"
 
 using namespace dbhip;
@@ -39,41 +42,6 @@ template <> struct UIntOf<1> { typedef uint8_t type; };
 template <> struct UIntOf<2> { typedef uint16_t type; };
 template <> struct UIntOf<4> { typedef uint32_t type; };
 template <> struct UIntOf<8> { typedef uint64_t type; };
-
-template <typename T> struct alignas(16) Vec16 { T v[16 / sizeof(T)]; };
-
-// ROWS consecutive values: 16-byte loads (or one value for a scalar column)
-template <typename T, int ROWS>
-__device__ __forceinline__ void dt_load(const void* base, bool scalar, int64_t first, T (&v)[ROWS]) {
-  constexpr int PER = 16 / sizeof(T);
-  static_assert(ROWS % PER == 0, "whole 16-byte vectors");
-  if (scalar) {
-    const T s = *(const T*)base;
-#pragma unroll
-    for (int k = 0; k < ROWS; ++k) v[k] = s;
-  } else {
-    const Vec16<T>* p = (const Vec16<T>*)((const T*)base + first);
-#pragma unroll
-    for (int q = 0; q < ROWS / PER; ++q) {
-      const Vec16<T> t = p[q];
-#pragma unroll
-      for (int k = 0; k < PER; ++k) v[q * PER + k] = t.v[k];
-    }
-  }
-}
-template <typename T, int ROWS>
-__device__ __forceinline__ void dt_store(void* base, int64_t first, const T (&v)[ROWS]) {
-  constexpr int PER = 16 / sizeof(T);
-  static_assert(ROWS % PER == 0, "whole 16-byte vectors");
-  Vec16<T>* p = (Vec16<T>*)((T*)base + first);
-#pragma unroll
-  for (int q = 0; q < ROWS / PER; ++q) {
-    Vec16<T> t;
-#pragma unroll
-    for (int k = 0; k < PER; ++k) t.v[k] = v[q * PER + k];
-    p[q] = t;
-  }
-}
 
 struct MapArgs {
   const void* in;
@@ -119,41 +87,21 @@ struct TruncOp {
 };
 
 template <typename Op>
-struct MapShape {
-  static constexpr int kNarrow = sizeof(typename Op::In) < sizeof(typename Op::Out) ? sizeof(typename Op::In) : sizeof(typename Op::Out);
-  static constexpr int kRows = 16 / kNarrow;
-};
-
-template <typename Op>
 __global__ __launch_bounds__(256) void dt_map_kernel(const MapArgs A) {
   typedef typename Op::In In;
   typedef typename Op::Out Out;
-  constexpr int ROWS = MapShape<Op>::kRows;
   __shared__ int64_t s_at[Op::kTable ? DT_MAX_TRANSITIONS : 1];
   __shared__ int32_t s_after[Op::kTable ? DT_MAX_TRANSITIONS : 1];
   if constexpr (Op::kTable) {
     for (int i = threadIdx.x; i < A.n_transitions; i += 256) { s_at[i] = A.at_utc_s[i]; s_after[i] = A.offset_after_s[i]; }
     __syncthreads();
   }
-  const bool scalar = A.scalar != 0;
-  const int64_t groups = A.n / ROWS;
-  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
-    In v[ROWS];
-    Out r[ROWS];
-    dt_load<In, ROWS>(A.in, scalar, g * ROWS, v);
-#pragma unroll
-    for (int k = 0; k < ROWS; ++k) r[k] = Op::apply(v[k], A, s_at, s_after);
-    dt_store<Out, ROWS>(A.out, g * ROWS, r);
-  }
-  // the last n mod ROWS rows, one per lane
-  const int64_t i = groups * ROWS + threadIdx.x;
-  if (blockIdx.x == 0 && i < A.n) ((Out*)A.out)[i] = Op::apply(((const In*)A.in)[scalar ? 0 : i], A, s_at, s_after);
+  map_rows<In, Out>(A.in, std::true_type(), A.scalar != 0, A.out, std::true_type(), A.n, [&](In v) { return Op::apply(v, A, s_at, s_after); });
 }
 
 template <typename Op>
 int32_t launch_map(const MapArgs& A, hipStream_t s) {
-  const int64_t groups = A.n / MapShape<Op>::kRows;
-  hipLaunchKernelGGL(dt_map_kernel<Op>, dim3(grid_for(groups, 256)), dim3(256), 0, s, A);
+  hipLaunchKernelGGL(dt_map_kernel<Op>, dim3(map_grid<typename Op::In, typename Op::Out>(A.n)), dim3(256), 0, s, A);
   DBHIP_LAUNCH_CHECK();
   return DBHIP_OK;
 }
@@ -206,14 +154,15 @@ __global__ __launch_bounds__(256) void dt_add_kernel(const AddArgs A) {
   for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
     T v[ROWS], r[ROWS];
     int64_t d[ROWS];
-    dt_load<T, ROWS>(A.src, A.src_scalar != 0, g * ROWS, v);
-    dt_load<int64_t, ROWS>(A.delta, A.delta_scalar != 0, g * ROWS, d);
+    map_fetch<T, ROWS>(A.src, std::true_type(), A.src_scalar != 0, g * ROWS, v);
+    map_fetch<int64_t, ROWS>(A.delta, std::true_type(), A.delta_scalar != 0, g * ROWS, d);
 #pragma unroll
     for (int k = 0; k < ROWS; ++k) r[k] = dt_add_row<TS>(A, v[k], d[k], g * ROWS + k, raised);
-    dt_store<T, ROWS>(A.out, g * ROWS, r);
+    map_store<T, ROWS>(A.out, std::true_type(), g * ROWS, r);
   }
   const int64_t i = groups * ROWS + threadIdx.x;
-  if (blockIdx.x == 0 && i < A.n) ((T*)A.out)[i] = dt_add_row<TS>(A, ((const T*)A.src)[A.src_scalar ? 0 : i], A.delta[A.delta_scalar ? 0 : i], i, raised);
+  if (blockIdx.x == 0 && i < A.n)
+    map_store_one<T>(A.out, i, dt_add_row<TS>(A, map_load_one<T>(A.src, A.src_scalar ? 0 : i), map_load_one<int64_t>(A.delta, A.delta_scalar ? 0 : i), i, raised));
   // every lane arrives here: one add per wave that raised at all
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) raised += __shfl_xor(raised, off, 64);
@@ -236,20 +185,20 @@ __global__ __launch_bounds__(256) void dt_diff_kernel(const DiffArgs A) {
   for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
     T x[ROWS], y[ROWS];
     int64_t r[ROWS];
-    dt_load<T, ROWS>(A.a, A.a_scalar != 0, g * ROWS, x);
-    dt_load<T, ROWS>(A.b, A.b_scalar != 0, g * ROWS, y);
+    map_fetch<T, ROWS>(A.a, std::true_type(), A.a_scalar != 0, g * ROWS, x);
+    map_fetch<T, ROWS>(A.b, std::true_type(), A.b_scalar != 0, g * ROWS, y);
 #pragma unroll
     for (int k = 0; k < ROWS; ++k) {
       if constexpr (TS) r[k] = dt_diff_ts(A.unit, x[k], y[k], A.offset);
       else r[k] = dt_diff_date(A.unit, x[k], y[k]);
     }
-    dt_store<int64_t, ROWS>(A.out, g * ROWS, r);
+    map_store<int64_t, ROWS>(A.out, std::true_type(), g * ROWS, r);
   }
   const int64_t i = groups * ROWS + threadIdx.x;
   if (blockIdx.x == 0 && i < A.n) {
-    const T x = ((const T*)A.a)[A.a_scalar ? 0 : i], y = ((const T*)A.b)[A.b_scalar ? 0 : i];
-    if constexpr (TS) A.out[i] = dt_diff_ts(A.unit, x, y, A.offset);
-    else A.out[i] = dt_diff_date(A.unit, x, y);
+    const T x = map_load_one<T>(A.a, A.a_scalar ? 0 : i), y = map_load_one<T>(A.b, A.b_scalar ? 0 : i);
+    if constexpr (TS) map_store_one<int64_t>(A.out, i, dt_diff_ts(A.unit, x, y, A.offset));
+    else map_store_one<int64_t>(A.out, i, dt_diff_date(A.unit, x, y));
   }
 }
 

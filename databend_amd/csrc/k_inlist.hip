@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "dev_common.h"
+#include "dev_map.h"
 #include "dev_strview.h"
 #include "runtime.h"
 #include "dev_inlist.h"
@@ -89,8 +90,7 @@ __global__ __launch_bounds__(256) void inlist_kernel(const InParams P) {
   for (uint32_t t = threadIdx.x; t < P.image_words / 4; t += 256) ((uint4*)in_lds)[t] = ((const uint4*)P.image)[t];   // (whole 16-byte units: inl_set_finish)
   __syncthreads();
   using T = typename S::T;
-  constexpr int R = S::R, PER = 16 / (int)sizeof(T);
-  struct alignas(16) Pack { T v[PER]; };
+  constexpr int R = S::R;
   const T* data = (const T*)P.data;
   const uint32_t lane = threadIdx.x & 63;
   constexpr int64_t WAVE_ROWS = 64 * R;
@@ -99,12 +99,7 @@ __global__ __launch_bounds__(256) void inlist_kernel(const InParams P) {
     const int64_t i0 = w0 + (int64_t)lane * R;
     T x[R];
     if (P.vector_loads && i0 + R <= P.n) {
-#pragma unroll
-      for (int c = 0; c < R / PER; ++c) {
-        const Pack p = *(const Pack*)(data + i0 + c * PER);
-#pragma unroll
-        for (int k = 0; k < PER; ++k) x[c * PER + k] = p.v[k];
-      }
+      map_load<T, R>(data, std::true_type(), i0, x);
     } else {
 #pragma unroll
       for (int k = 0; k < R; ++k) x[k] = i0 + k < P.n ? data[P.is_scalar ? 0 : i0 + k] : T{};

@@ -8,13 +8,14 @@
 // lane by the first workgroup. A scalar source is read once per lane. The function code, the decoded digits (MtNum) and the decoded
 // decimal call (MtDec) travel in the argument struct, so every branch on them is wave-uniform.
 // Sliced columns: data and out need only be aligned to their element (a Decimal128 to 8 bytes). A wave-uniform test of each base picks
-// the 16-byte form or a per-element form of the load and of the store, independently (as dev_load.h does for its quads). The loader
-// restates k_datetime.hip's dt_load / dt_store / MapShape, which live in that file's anonymous namespace and have no such fallback.
+// the 16-byte form or a per-element form of the load and of the store, independently (as dev_load.h does for its quads). The loop, the
+// tail rule and both forms of every access are dev_map.h's map_rows, which k_datetime.hip's kernels use as well.
 // No LDS, no scratch memory, no atomics. Validity is not touched: it passes through (the binding reuses the source's Bitmap).
 #include <string.h>
 
 #include <type_traits>
 
+#include "dev_map.h"
 #include "dev_math.h"
 #include "runtime.h"
 
@@ -33,67 +34,6 @@ struct MathArgs {
   MtNum num;
   MtDec dec;
 };
-
-template <typename T> struct alignas(16) Vec16 { T v[16 / sizeof(T)]; };
-
-// one value from an address aligned to the element; a 16-byte value (Decimal128) as two 8-byte words
-template <typename T>
-__device__ __forceinline__ T mt_load_one(const void* base, int64_t i) {
-  if constexpr (sizeof(T) == 16) {
-    const uint64_t* p = (const uint64_t*)base + 2 * i;
-    return (T)(((mt_u128)p[1] << 64) | p[0]);
-  } else {
-    return ((const T*)base)[i];
-  }
-}
-template <typename T>
-__device__ __forceinline__ void mt_store_one(void* base, int64_t i, T v) {
-  if constexpr (sizeof(T) == 16) {
-    uint64_t* p = (uint64_t*)base + 2 * i;
-    p[0] = (uint64_t)(mt_u128)v;
-    p[1] = (uint64_t)((mt_u128)v >> 64);
-  } else {
-    ((T*)base)[i] = v;
-  }
-}
-
-// ROWS consecutive values from row `first`: 16-byte loads when the base is 16-byte aligned (first * sizeof(T) is a multiple of 16 by
-// the choice of ROWS), element loads otherwise
-template <typename T, int ROWS>
-__device__ __forceinline__ void mt_load(const void* base, bool vec, int64_t first, T (&v)[ROWS]) {
-  constexpr int PER = 16 / sizeof(T);
-  static_assert(ROWS % PER == 0, "whole 16-byte vectors");
-  if (vec) {
-    const Vec16<T>* p = (const Vec16<T>*)((const char*)base + first * (int64_t)sizeof(T));
-#pragma unroll
-    for (int q = 0; q < ROWS / PER; ++q) {
-      const Vec16<T> t = p[q];
-#pragma unroll
-      for (int k = 0; k < PER; ++k) v[q * PER + k] = t.v[k];
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < ROWS; ++k) v[k] = mt_load_one<T>(base, first + k);
-  }
-}
-template <typename T, int ROWS>
-__device__ __forceinline__ void mt_store(void* base, bool vec, int64_t first, const T (&v)[ROWS]) {
-  constexpr int PER = 16 / sizeof(T);
-  static_assert(ROWS % PER == 0, "whole 16-byte vectors");
-  if (vec) {
-    Vec16<T>* p = (Vec16<T>*)((char*)base + first * (int64_t)sizeof(T));
-#pragma unroll
-    for (int q = 0; q < ROWS / PER; ++q) {
-      Vec16<T> t;
-#pragma unroll
-      for (int k = 0; k < PER; ++k) t.v[k] = v[q * PER + k];
-      p[q] = t;
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < ROWS; ++k) mt_store_one<T>(base, first + k, v[k]);
-  }
-}
 
 // ---- the function classes: In and Out are what moves through memory ------------------------------------------------------------------
 template <typename S>
@@ -133,45 +73,19 @@ struct DecOp {   // ABS, CEIL, FLOOR, ROUND, TRUNCATE of a decimal: the storage 
   }
 };
 
+// at least 7 waves per SIMD: SignOp<__int128> holds 16 loaded quads and would otherwise take 73 VGPRs, one past the step from 7 to 6
 template <typename Op>
-struct MapShape {
-  static constexpr int kNarrow = sizeof(typename Op::In) < sizeof(typename Op::Out) ? sizeof(typename Op::In) : sizeof(typename Op::Out);
-  static constexpr int kRows = 16 / kNarrow;
-};
-
-template <typename Op>
-__global__ __launch_bounds__(256) void math_map_kernel(const MathArgs A) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void math_map_kernel(const MathArgs A) {
   typedef typename Op::In In;
   typedef typename Op::Out Out;
-  constexpr int ROWS = MapShape<Op>::kRows;
-  const bool scalar = A.scalar != 0;
   // read from the kernel arguments alone: wave-uniform
   const bool in_vec = ((unsigned long long)A.in & 15) == 0, out_vec = ((unsigned long long)A.out & 15) == 0;
-  const int64_t groups = A.n / ROWS;
-  In s = In();
-  if (scalar) s = mt_load_one<In>(A.in, 0);
-  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
-    In v[ROWS];
-    Out r[ROWS];
-    if (scalar) {
-#pragma unroll
-      for (int k = 0; k < ROWS; ++k) v[k] = s;
-    } else {
-      mt_load<In, ROWS>(A.in, in_vec, g * ROWS, v);
-    }
-#pragma unroll
-    for (int k = 0; k < ROWS; ++k) r[k] = Op::apply(v[k], A);
-    mt_store<Out, ROWS>(A.out, out_vec, g * ROWS, r);
-  }
-  // the last n mod ROWS rows, one per lane
-  const int64_t i = groups * ROWS + threadIdx.x;
-  if (blockIdx.x == 0 && i < A.n) mt_store_one<Out>(A.out, i, Op::apply(scalar ? s : mt_load_one<In>(A.in, i), A));
+  map_rows<In, Out>(A.in, in_vec, A.scalar != 0, A.out, out_vec, A.n, [&A](In v) { return Op::apply(v, A); });
 }
 
 template <typename Op>
 int32_t launch_map(const MathArgs& A, hipStream_t s) {
-  const int64_t groups = A.n / MapShape<Op>::kRows;
-  hipLaunchKernelGGL(math_map_kernel<Op>, dim3(grid_for(groups, 256)), dim3(256), 0, s, A);
+  hipLaunchKernelGGL(math_map_kernel<Op>, dim3(map_grid<typename Op::In, typename Op::Out>(A.n)), dim3(256), 0, s, A);
   DBHIP_LAUNCH_CHECK();
   return DBHIP_OK;
 }

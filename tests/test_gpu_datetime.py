@@ -148,7 +148,8 @@ TAIL_N = [0, 1, 15, 16, 17, 63, 64, 65, 1023, 1025, 4099]
 @pytest.mark.parametrize("n", TAIL_N)
 def test_lane_tails(gpu, n):
     """one U8, one U16, one U32 and one U64 part and a truncation at every n: as a plain column, as a nullable column whose Bitmap starts
-    at bit 3 (validity passes through untouched), and as a scalar"""
+    at bit 3 (validity passes through untouched), and as a scalar; then an addition and a difference by days of Dates and of
+    Timestamps, the second operand once a column and once a scalar"""
     rng = np.random.default_rng(2106 + n)
     dates = rng.integers(R.DATE_MIN, R.DATE_MAX + 1, max(n, 1))[:n]
     ts = rng.integers(R.TS_MIN, R.TS_MAX + 1, max(n, 1))[:n]
@@ -173,6 +174,29 @@ def test_lane_tails(gpu, n):
             same(run_trunc(gpu, R.U_MONTH, 0, col, out, n, -34200), R.trunc(R.U_MONTH, 0, v, src, out, -34200), ("trunc", src, out, n))
         one = int(v[0]) if n else 0
         same(run_trunc(gpu, R.U_MONTH, 0, scalar(gpu, one, src), out, n, -34200), R.trunc(R.U_MONTH, 0, np.full(n, one), src, out, -34200), ("trunc scalar", n))
+    # add and diff by days, the second operand once a column and once a scalar; every value lies 50 days inside the range and no delta
+    # exceeds 40 days, so no row may raise
+    deltas = rng.integers(-40, 41, max(n, 1))[:n]
+    for src, v, margin, offset in ((R.SRC_DATE, dates, 50, 0), (R.SRC_TS, ts, 50 * R.DAY_US, 19800)):
+        lo, hi = (R.DATE_MIN, R.DATE_MAX) if src == R.SRC_DATE else (R.TS_MIN, R.TS_MAX)
+        v = np.clip(v, lo + margin, hi - margin)
+        col = column(gpu, v if n else [0], src)
+        for what, dcol, d in (("column", gpu.Column.from_numpy(deltas if n else np.zeros(1, np.int64), T.T_I64), deltas), ("scalar", gpu.Column.scalar(-37, T.T_I64), -37)):
+            got, bad, count = run_add(gpu, R.U_DAY, col, dcol, n, offset)
+            exp, ebad = R.add(R.U_DAY, v, d, src, offset)
+            assert not ebad.any() and not bad.any() and count == 0, ("add", src, what, n, int(bad.sum()), count)
+            same(got, exp, ("add", src, what, n))
+        other = np.clip(v + deltas * (margin // 50) - 1, lo, hi)
+        same(run_diff(gpu, R.U_DAY, col, column(gpu, other if n else [0], src), n, offset), R.diff(R.U_DAY, v, other, src, offset), ("diff column", src, n))
+        one = int(other[0]) if n else 0
+        same(run_diff(gpu, R.U_DAY, col, scalar(gpu, one, src), n, offset), R.diff(R.U_DAY, v, np.array([one]), src, offset), ("diff scalar", src, n))
+        # a scalar first operand
+        same(run_diff(gpu, R.U_DAY, scalar(gpu, one, src), col, n, offset), R.diff(R.U_DAY, np.array([one]), v, src, offset), ("diff scalar a", src, n))
+        if n:
+            got, bad, count = run_add(gpu, R.U_DAY, scalar(gpu, int(v[0]), src), gpu.Column.from_numpy(deltas, T.T_I64), n, offset)
+            exp, ebad = R.add(R.U_DAY, np.full(n, int(v[0])), deltas, src, offset)
+            assert not ebad.any() and not bad.any() and count == 0, ("add scalar source", src, n, int(bad.sum()), count)
+            same(got, exp, ("add scalar source", src, n))
 
 
 # ---- truncation -------------------------------------------------------------------------------------------------------------------------
