@@ -149,6 +149,11 @@ pub const DBHIP_BOOL_AND: i32 = 0;   // dbhip_bool_op
 pub const DBHIP_BOOL_OR: i32 = 1;   // dbhip_bool_op
 pub const DBHIP_BOOL_NOT: i32 = 2;   // dbhip_bool_op
 pub const DBHIP_BOOL_XOR: i32 = 3;   // dbhip_bool_op
+pub const DBHIP_STRW_REPLACE: i32 = 0;   // dbhip_str_rewrite_op
+pub const DBHIP_STRW_LPAD: i32 = 1;   // dbhip_str_rewrite_op
+pub const DBHIP_STRW_RPAD: i32 = 2;   // dbhip_str_rewrite_op
+pub const DBHIP_STRW_REPEAT: i32 = 3;   // dbhip_str_rewrite_op
+pub const DBHIP_STRW_REVERSE: i32 = 4;   // dbhip_str_rewrite_op
 pub const DBHIP_VEC_COSINE: i32 = 0;   // dbhip_vec_metric
 pub const DBHIP_VEC_L2: i32 = 1;   // dbhip_vec_metric
 pub const DBHIP_VEC_DOT: i32 = 2;   // dbhip_vec_metric
@@ -435,6 +440,10 @@ extern "C" {
     pub fn dbhip_case(conds_host: *const dbhip_col, n_conds: i32, values_host: *const dbhip_col, n: i64, out: *mut c_void, out_validity: *mut u8, out_branch: *mut u8, out_buffers_dev: *mut *const c_void, out_n_buffers_host: *mut i32, stream: *mut c_void) -> i32;
     pub fn dbhip_coalesce(args_host: *const dbhip_col, n_args: i32, n: i64, out: *mut c_void, out_validity: *mut u8, out_branch: *mut u8, out_buffers_dev: *mut *const c_void, out_n_buffers_host: *mut i32, stream: *mut c_void) -> i32;
     pub fn dbhip_bool_logic(op: i32, a: *const dbhip_col, b: *const dbhip_col, n: i64, out_values: *mut u8, out_validity: *mut u8, stream: *mut c_void) -> i32;
+    pub fn dbhip_str_position(col: *const dbhip_col, needle_host: *const u8, needle_len: i32, start: *const dbhip_col, flags: i32, n: i64, out: *mut u64, stream: *mut c_void) -> i32;
+    pub fn dbhip_str_split_part(col: *const dbhip_col, delim_host: *const u8, delim_len: i32, part: *const dbhip_col, n: i64, out_views: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn dbhip_str_rewrite_bytes(op: i32, col: *const dbhip_col, k: *const dbhip_col, x_host: *const u8, x_len: i32, y_host: *const u8, y_len: i32, flags: i32, n: i64, out_bytes_host: *mut u64, stream: *mut c_void) -> i32;
+    pub fn dbhip_str_rewrite(op: i32, col: *const dbhip_col, k: *const dbhip_col, x_host: *const u8, x_len: i32, y_host: *const u8, y_len: i32, flags: i32, n: i64, out_views: *mut c_void, out_data: *mut u8, out_data_bytes: u64, err_count_dev: *mut u64, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_distance_rows(metric: i32, elem_type: i32, lhs: *const c_void, lhs_is_scalar: i32, rhs: *const c_void, rhs_is_scalar: i32, n: i64, dim: i32, out: *mut c_void, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_distance(metric: i32, base: *const f32, n: i64, dim: i32, queries: *const f32, nq: i32, out: *mut f32, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_topk(metric: i32, base: *const f32, n: i64, dim: i32, queries: *const f32, nq: i32, k: i32, out_idx: *mut u32, out_dist: *mut f32, stream: *mut c_void) -> i32;

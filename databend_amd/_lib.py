@@ -132,6 +132,9 @@ REGEX_MAX_PATTERN, REGEX_MAX_STATES, REGEX_MAX_TABLE_BYTES = 1024, 4096, 32768
 # DBHIP_STR_PARSE_MAX_BYTES: dbhip_str_parse declines a longer value unread
 STR_PARSE_MAX_BYTES = 256
 
+# dbhip_str_rewrite_op (the flag of the group is STR_UNIT_BYTE)
+STRW_REPLACE, STRW_LPAD, STRW_RPAD, STRW_REPEAT, STRW_REVERSE = range(5)
+
 # dbhip_math_fn
 MATH_ABS, MATH_SIGN, MATH_CEIL, MATH_FLOOR, MATH_ROUND, MATH_TRUNCATE, MATH_SQRT = range(7)
 
@@ -166,7 +169,8 @@ SYMBOLS = [
     "dbhip_join_destroy", "dbhip_join_mark_build", "dbhip_join_build_matched", "dbhip_sort_perm", "dbhip_merge_sorted_perm", "dbhip_sort_bound_partition",
     "dbhip_window_bounds", "dbhip_window_rank", "dbhip_window_shift", "dbhip_window_value", "dbhip_window_aggregate",
     "dbhip_like_kind", "dbhip_like", "dbhip_str_match", "dbhip_dt_part_type", "dbhip_dt_part", "dbhip_dt_trunc", "dbhip_dt_add", "dbhip_dt_diff", "dbhip_str_length", "dbhip_str_slice", "dbhip_str_build_bytes", "dbhip_str_build",
-    "dbhip_inlist_create", "dbhip_inlist_path", "dbhip_inlist_eval", "dbhip_inlist_destroy", "dbhip_str_parse", "dbhip_str_format_bytes", "dbhip_str_format", "dbhip_regex_check", "dbhip_regex_create", "dbhip_regex_eval", "dbhip_regex_destroy", "dbhip_math_result", "dbhip_math", "dbhip_case_check", "dbhip_case", "dbhip_coalesce", "dbhip_bool_logic", "dbhip_bitmap_set_indices", "dbhip_siphash64", "dbhip_scatter_indices", "dbhip_scatter_block", "dbhip_vec_distance", "dbhip_vec_distance_rows", "dbhip_vec_topk", "dbhip_score_u8",
+    "dbhip_inlist_create", "dbhip_inlist_path", "dbhip_inlist_eval", "dbhip_inlist_destroy", "dbhip_str_parse", "dbhip_str_format_bytes", "dbhip_str_format", "dbhip_regex_check", "dbhip_regex_create", "dbhip_regex_eval", "dbhip_regex_destroy", "dbhip_math_result", "dbhip_math", "dbhip_case_check", "dbhip_case", "dbhip_coalesce", "dbhip_bool_logic",
+    "dbhip_str_position", "dbhip_str_split_part", "dbhip_str_rewrite_bytes", "dbhip_str_rewrite", "dbhip_bitmap_set_indices", "dbhip_siphash64", "dbhip_scatter_indices", "dbhip_scatter_block", "dbhip_vec_distance", "dbhip_vec_distance_rows", "dbhip_vec_topk", "dbhip_score_u8",
     "dbhip_vec_topk_merge", "dbhip_vec_index_build", "dbhip_vec_index_search", "dbhip_vec_index_destroy",
     "dbhip_comm_unique_id", "dbhip_comm_create", "dbhip_comm_destroy", "dbhip_comm_abort", "dbhip_comm_allgather", "dbhip_comm_alltoall",
     "dbhip_comm_allreduce_sum_u64", "dbhip_groupby_exchange_allgather", "dbhip_groupby_exchange_alltoall", "dbhip_kmeans", "dbhip_vec_kernel_f32", "dbhip_hnsw_build", "dbhip_hnsw_build_sequential", "dbhip_hnsw_from_graph", "dbhip_hnsw_open", "dbhip_hnsw_export_graph", "dbhip_hnsw_search", "dbhip_hnsw_scores",
@@ -233,6 +237,14 @@ def load_library():
                                   C.c_void_p, C.c_void_p]
     L.dbhip_str_format_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
     L.dbhip_str_format.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    # String search and rewrite: (col, needle, len, start, flags, n, out, stream) / (col, delim, len, part, n, out_views, stream) /
+    # (op, col, k, x, x_len, y, y_len, flags, n, out_bytes_host, stream) / (op, col, k, x, x_len, y, y_len, flags, n, out_views, out_data,
+    # out_data_bytes, err_count, stream)
+    L.dbhip_str_position.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
+    L.dbhip_str_split_part.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.dbhip_str_rewrite_bytes.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
+    L.dbhip_str_rewrite.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
+                                    C.c_uint64, C.c_void_p, C.c_void_p]
     # the math group: (fn, src_type, src_precision, src_scale, digits, out_type, out_precision, out_scale) / (fn, src, digits, n, out, stream)
     L.dbhip_math_result.argtypes = [C.c_int32, C.c_int32, C.c_uint8, C.c_uint8, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.dbhip_math.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]

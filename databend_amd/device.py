@@ -794,6 +794,101 @@ def lower(col, n=None):
     return _str_build(L.STR_LOWER, [col], n)
 
 
+def _str_rows(col, n, *args):
+    """the row count of a call: n, or the column's, or (a scalar column) the longest non-scalar argument's"""
+    if n is not None:
+        return n
+    return col.n if not col.is_scalar else max([x.n for x in args if x is not None and not x.is_scalar], default=col.n)
+
+
+def position(col, needle, start=None, unit_byte=False, n=None):
+    """position(needle IN col) / locate(needle, col[, start]) / instr / strpos (dbhip_str_position): the 1-based unit position of the
+    first occurrence at or behind unit `start` (a Python int or an Int64 Column; None = 1), 0 when there is none -> UInt64 Column with
+    the source's validity"""
+    start = _i64_arg(start)
+    n = _str_rows(col, n, start)
+    out = DeviceBuffer(max(n, 1) * 8)
+    cc = col.c()
+    cs = start.c() if start is not None else None
+    buf, ln = _host_bytes(needle)
+    check(lib().dbhip_str_position(C.byref(cc), buf, C.c_int32(ln), C.byref(cs) if cs is not None else None, C.c_int32(L.STR_UNIT_BYTE if unit_byte else 0),
+                                   C.c_int64(n), C.c_void_p(out.ptr), None))
+    res = _same_validity(col, n, L.T_U64, out)
+    res._keep = tuple(x for x in (col, start) if x is not None)
+    return res
+
+
+def split_part(col, delim, part, n=None):
+    """split_part(col, delim, part) (dbhip_str_split_part): the part-th field between the occurrences of the constant `delim`, a negative
+    part counted from the end -> String Column that shares col's buffer table (no byte is copied) and keeps col's validity"""
+    part = _i64_arg(part)
+    n = _str_rows(col, n, part)
+    out = DeviceBuffer(max(n, 1) * 16)
+    cc, cp = col.c(), part.c()
+    buf, ln = _host_bytes(delim)
+    check(lib().dbhip_str_split_part(C.byref(cc), buf, C.c_int32(ln), C.byref(cp), C.c_int64(n), C.c_void_p(out.ptr), None))
+    if col.is_scalar:
+        res = _nullable(Column(L.T_STRING, n, out, buffers=col.buffers, keep=(col, part)), _merged_validity(col, col, n))
+    else:
+        res = Column(L.T_STRING, n, out, col.validity, buffers=col.buffers, keep=(col, part))
+        res.voff = col.voff
+    res.n_buffers = col.n_buffers
+    return res
+
+
+def _str_rewrite(op, col, k=None, x=b"", y=b"", unit_byte=False, n=None):
+    """dbhip_str_rewrite_bytes + dbhip_str_rewrite -> String Column with its own data buffer (kept alive by the Column) and the source's
+    validity. res.str_counters: a DeviceBuffer of one u64, the rows that did not fit or whose result is longer than 2^32 - 1 bytes (they
+    hold the empty view)."""
+    k = _i64_arg(k)
+    n = _str_rows(col, n, k)
+    cc = col.c()
+    ck = k.c() if k is not None else None
+    kref = C.byref(ck) if ck is not None else None
+    xb, xl = _host_bytes(x)
+    yb, yl = _host_bytes(y)
+    flags = C.c_int32(L.STR_UNIT_BYTE if unit_byte else 0)
+    nbytes = C.c_uint64(0)
+    check(lib().dbhip_str_rewrite_bytes(C.c_int32(op), C.byref(cc), kref, xb, C.c_int32(xl), yb, C.c_int32(yl), flags, C.c_int64(n), C.byref(nbytes), None))
+    data = DeviceBuffer(nbytes.value)
+    views = DeviceBuffer(max(n, 1) * 16)
+    counters = DeviceBuffer(8).zero()
+    check(lib().dbhip_str_rewrite(C.c_int32(op), C.byref(cc), kref, xb, C.c_int32(xl), yb, C.c_int32(yl), flags, C.c_int64(n), C.c_void_p(views.ptr),
+                                  C.c_void_p(data.ptr), C.c_uint64(nbytes.value), C.c_void_p(counters.ptr), None))
+    ptrs = DeviceBuffer.from_numpy(np.array([data.ptr], dtype=np.uint64))
+    res = _same_validity(col, n, L.T_STRING, views)
+    res.buffers, res.n_buffers = ptrs, 1
+    res._keep = (data, col) + ((k,) if k is not None else ())
+    res.str_counters = counters
+    return res
+
+
+def replace(col, frm, to, n=None):
+    """replace(col, from, to): every greedy left-to-right non-overlapping occurrence of the constant `frm` replaced by `to`; an empty
+    `frm` gives the value unchanged"""
+    return _str_rewrite(L.STRW_REPLACE, col, None, frm, to, n=n)
+
+
+def lpad(col, length, pad, unit_byte=False, n=None):
+    """lpad(col, length, pad): cut or filled in front to `length` units (a Python int or an Int64 Column) with the constant pad's units"""
+    return _str_rewrite(L.STRW_LPAD, col, length, pad, unit_byte=unit_byte, n=n)
+
+
+def rpad(col, length, pad, unit_byte=False, n=None):
+    """rpad(col, length, pad): cut or filled behind to `length` units (see lpad)"""
+    return _str_rewrite(L.STRW_RPAD, col, length, pad, unit_byte=unit_byte, n=n)
+
+
+def repeat(col, k, n=None):
+    """repeat(col, k): the value k times (a Python int or an Int64 Column); space(k) is repeat of a scalar ' '"""
+    return _str_rewrite(L.STRW_REPEAT, col, k, n=n)
+
+
+def reverse(col, unit_byte=False, n=None):
+    """reverse(col): the UTF-8 units in reverse order (the bytes with unit_byte)"""
+    return _str_rewrite(L.STRW_REVERSE, col, unit_byte=unit_byte, n=n)
+
+
 def parse_strings(col, dtype, precision=0, scale=0, is_try=False, rounding_mode=False, offset_s=0, n=None, errors=None):
     """to_int8 .. to_uint64 / to_decimal(p, s) / to_date / to_timestamp and their try_ forms on a String column (dbhip_str_parse) ->
     (Column, declined): `declined` is the number of rows the device did not decide (they hold 0): when it is not zero the caller

@@ -41,7 +41,7 @@ extern "C" {
 #endif
 
 #define DBHIP_ABI_VERSION 6   /* 6 (round 6): pipelined fused aggregation (dbhip_groupby_set_pipelined / dbhip_groupby_checkpoint), and (backward
-                                 compatible, same version) DELTA_(LENGTH_)BYTE_ARRAY / BYTE_STREAM_SPLIT on the device with dbhip_pq_chunk_take_arena; likewise the Date / Timestamp functions (a21: dbhip_dt_part / _trunc / _add / _diff, DBHIP_EX_DT_PART / DBHIP_EX_DT_TRUNC), the math functions (a26: dbhip_math_result / dbhip_math) and the conditionals (a27: dbhip_case_check / dbhip_case / dbhip_coalesce / dbhip_bool_logic; 196 functions in all); 5 (round 5): ZSTD on the device, batched chunk decode (dbhip_pq_chunks_decode_device); 4 (round 4): block scatter / concat, exchange and plan calls, device-mode scan, cancellation, row-wise vector distance */
+                                 compatible, same version) DELTA_(LENGTH_)BYTE_ARRAY / BYTE_STREAM_SPLIT on the device with dbhip_pq_chunk_take_arena; likewise the Date / Timestamp functions (a21: dbhip_dt_part / _trunc / _add / _diff, DBHIP_EX_DT_PART / DBHIP_EX_DT_TRUNC), the math functions (a26: dbhip_math_result / dbhip_math) the conditionals (a27: dbhip_case_check / dbhip_case / dbhip_coalesce / dbhip_bool_logic) and String search and rewrite (a28: dbhip_str_position / dbhip_str_split_part / dbhip_str_rewrite_bytes / dbhip_str_rewrite; 200 functions in all); 5 (round 5): ZSTD on the device, batched chunk decode (dbhip_pq_chunks_decode_device); 4 (round 4): block scatter / concat, exchange and plan calls, device-mode scan, cancellation, row-wise vector distance */
 
 /* ---- status codes ------------------------------------------------------- */
 enum {
@@ -1395,6 +1395,81 @@ int32_t dbhip_coalesce(const dbhip_col* args_host, int32_t n_args, int64_t n, vo
                        const void** out_buffers_dev, int32_t* out_n_buffers_host, void* stream);
 int32_t dbhip_bool_logic(int32_t op, const dbhip_col* a, const dbhip_col* b /* NULL for NOT */, int64_t n,
                          uint8_t* out_values, uint8_t* out_validity, void* stream);
+/* jit-embed: resume */
+
+/* jit-embed: skip (as a19: the run-time compiled kernels never see this group; the codes the kernels use are restated in csrc/dev_strsearch.h) */
+/* ---- a28: String search and rewrite: position / locate, split_part, replace, lpad / rpad, repeat, reverse ----------
+ * Replaces the closures behind position / locate / instr / strpos (as a VALUE; dbhip_str_match answers only `position(..) > 0`),
+ * split_part, replace, lpad, rpad, repeat / space and reverse with a CONSTANT needle / from / to / pad / delimiter (INTEGRATION.md §23
+ * maps the names): the list a22 left out of scope. The reference's source is not at hand, so this comment is the definition;
+ * csrc/dev_strsearch.h implements the row logic once, for the kernels and for the host checker (tests/strsearch_host_check.cpp).
+ *
+ * Column. As a22, word for word: `col` must be DBHIP_T_STRING, else DBHIP_ERR_INVALID; views 16-byte aligned; is_scalar is allowed;
+ * validity and validity_offset are honoured. n = 0 returns DBHIP_OK before any launch; n > 2^32 - 2 is DBHIP_ERR_INVALID. A NULL row is
+ * never dereferenced: its result is 0, or the all-zero view. A long view whose buffer index is >= n_buffers, or whose table entry is
+ * NULL, is never dereferenced either: its result is 0, or the empty view. Value bytes are read only with loads that lie inside the
+ * value's own naturally aligned 4-byte words: data buffers need no padding. An inline result (len <= 12) is canonical. `start`, `part`
+ * and `k` are DBHIP_T_I64 columns or scalars whose validity is not read (the binding merges validities). There is no out_validity:
+ * the binding reuses the source's Bitmap, as for dbhip_str_slice. The stream stays usable after every refusal.
+ *
+ * Constants. needle / from / to / pad / delimiter are host bytes, 0..255 of them: more is DBHIP_ERR_UNSUPPORTED before any launch (keep
+ * the CPU closure); a negative length, or a NULL pointer with a positive length, is DBHIP_ERR_INVALID. `flags` is DBHIP_STR_UNIT_BYTE or
+ * 0; any other bit is DBHIP_ERR_INVALID. Units and boundaries are a22's: the boundaries of a value are position 0, position len and
+ * every byte not of the form 10xxxxxx; with DBHIP_STR_UNIT_BYTE a unit is one byte. U below is the value's unit count.
+ *
+ * Matching is bytewise and case-sensitive. "The occurrences" of a needle are the GREEDY LEFT-TO-RIGHT NON-OVERLAPPING ones: the first
+ * at the smallest byte position p0 >= 0, the next at the smallest p >= pk + needle_len. `aa` occurs in `aaaaa` at 0 and at 2.
+ *
+ * dbhip_str_position: position(needle IN col), locate(needle, col[, start]), instr, strpos. `out`: n u64, 8-byte aligned. Let s =
+ * start (1 when `start` is a NULL pointer). s <= 0: 0. s > U + 1: 0. Otherwise the search begins at byte position b = the (s - 1)-th
+ * boundary (byte mode: s - 1). An empty needle: the result is s. Otherwise let p be the smallest byte position >= b with
+ * value[p .. p + needle_len) == needle: none gives 0, else the result is 1 + (the number of boundaries q with 0 < q <= p), in byte mode
+ * p + 1. On valid UTF-8 with a valid needle this is the 1-based character position; on arbitrary bytes it is still defined. Decided
+ * by comparisons before any arithmetic: every i64 start is defined.
+ *
+ * dbhip_str_split_part: split_part(col, delim, part). The result is a sub-range of the source: no byte is copied, the output column
+ * shares the source's buffer table and the result view is dbhip_str_slice's. The fields are the pieces between the occurrences of
+ * `delim`: c occurrences give c + 1 fields, which may be empty; an empty `delim` gives one field, the whole value. part = 0 is treated
+ * as 1; part > 0 is the part-th field; part < 0 the |part|-th field from the end of the same list; a part beyond the list, either
+ * way, gives the empty view. INT64_MIN and INT64_MAX are defined (comparisons). out_views: n views, 16-byte aligned.
+ *
+ * dbhip_str_rewrite_bytes / dbhip_str_rewrite: results that need new bytes, with dbhip_str_build's two-call protocol. _bytes drains
+ * the stream and writes to the host the total bytes of the results longer than 12; the caller allocates exactly that much and calls
+ * _rewrite with the same arguments: the long results lie back to back in row order without padding, their views are {len, first four
+ * bytes, index 0, offset}; shorter results are inline. The kernels never write at or past out_data_bytes: a row whose bytes do not fit,
+ * that would end past offset 2^32, or whose result is longer than 2^32 - 1 bytes gets the empty view and is added to *err_count_dev
+ * (may be NULL; 8-byte aligned). A result's length is decided by comparisons before any multiply: repeat(x, INT64_MAX) and
+ * lpad(x, INT64_MAX, 'ab') are "too long", not overflowed arithmetic; _bytes counts 0 for such a row.
+ *   REPLACE        x = from, y = to. Every occurrence of x is replaced by y; an empty x gives the value unchanged. k and the unit flag
+ *                  are ignored. Length = len + c * (y_len - x_len).
+ *   LPAD / RPAD    x = pad, k = the target length L in units. L <= 0: empty. L <= U: the first L units of the value (both ops). L > U
+ *                  with an empty pad: empty. L > U otherwise: F = L - U fill units, taken from the pad's own units cyclically from its
+ *                  first, in front of the value (LPAD) or behind it (RPAD). Byte mode: units are bytes throughout. y is ignored.
+ *                  lpad('hi', 5, 'xy') = 'xyxhi'; rpad('hi', 1, 'x') = 'h'.
+ *   REPEAT         k = the count. k <= 0, or an empty value: empty; otherwise the value k times. x, y and the unit flag are ignored.
+ *   REVERSE        the units in reverse order, each unit's bytes in their own order; byte mode: the bytes reversed. k, x, y are ignored.
+ * An op outside the enum is DBHIP_ERR_INVALID, as is a `k` that is missing or not DBHIP_T_I64 where the op needs it. An argument an op
+ * ignores is not looked at.
+ *
+ * Calls. Asynchronous on `stream` except dbhip_str_rewrite_bytes; scratch comes from the (thread, stream) scratch; cancellation is
+ * polled between the launches. As in a22 no lane walks more than DBHIP_LIKE_LONG_BYTES bytes of one value serially and no lane copies
+ * more than that: a longer value that needs a search or a walk, and a longer result, go through a row list in scratch (4 bytes per
+ * row of the call) to a wave-per-row pass that reads the list's length on the device and searches 64 aligned words per step.
+ * Out of scope: a needle / from / to / pad / delimiter that is a column; nullable start / part / k; regexp_replace, translate, insert;
+ * split to an Array; ops inside dbhip_expr_eval programs; the C++ host mirror and the Rust shim (which wrap none of a21 - a27 either). */
+typedef enum { DBHIP_STRW_REPLACE = 0, DBHIP_STRW_LPAD = 1, DBHIP_STRW_RPAD = 2, DBHIP_STRW_REPEAT = 3, DBHIP_STRW_REVERSE = 4 } dbhip_str_rewrite_op;
+
+int32_t dbhip_str_position(const dbhip_col* col, const uint8_t* needle_host, int32_t needle_len,
+                           const dbhip_col* start /* I64 column or scalar; NULL = 1 */, int32_t flags, int64_t n, uint64_t* out,
+                           void* stream);
+int32_t dbhip_str_split_part(const dbhip_col* col, const uint8_t* delim_host, int32_t delim_len,
+                             const dbhip_col* part /* I64 column or scalar */, int64_t n, void* out_views, void* stream);
+int32_t dbhip_str_rewrite_bytes(int32_t op, const dbhip_col* col, const dbhip_col* k /* I64; LPAD / RPAD length, REPEAT count; else NULL */,
+                                const uint8_t* x_host, int32_t x_len, const uint8_t* y_host, int32_t y_len, int32_t flags, int64_t n,
+                                uint64_t* out_bytes_host, void* stream);
+int32_t dbhip_str_rewrite(int32_t op, const dbhip_col* col, const dbhip_col* k, const uint8_t* x_host, int32_t x_len,
+                          const uint8_t* y_host, int32_t y_len, int32_t flags, int64_t n, void* out_views, uint8_t* out_data,
+                          uint64_t out_data_bytes, uint64_t* err_count_dev, void* stream);
 /* jit-embed: resume */
 
 /* ---- a17/a18: vector distance ------------------------------------------------
