@@ -154,6 +154,12 @@ pub const DBHIP_STRW_LPAD: i32 = 1;   // dbhip_str_rewrite_op
 pub const DBHIP_STRW_RPAD: i32 = 2;   // dbhip_str_rewrite_op
 pub const DBHIP_STRW_REPEAT: i32 = 3;   // dbhip_str_rewrite_op
 pub const DBHIP_STRW_REVERSE: i32 = 4;   // dbhip_str_rewrite_op
+pub const DBHIP_ARR_COUNT: i32 = 0;   // dbhip_array_reduce_kind
+pub const DBHIP_ARR_SUM: i32 = 1;   // dbhip_array_reduce_kind
+pub const DBHIP_ARR_MIN: i32 = 2;   // dbhip_array_reduce_kind
+pub const DBHIP_ARR_MAX: i32 = 3;   // dbhip_array_reduce_kind
+pub const DBHIP_ARR_CONTAINS: i32 = 0;   // dbhip_array_find_op
+pub const DBHIP_ARR_INDEXOF: i32 = 1;   // dbhip_array_find_op
 pub const DBHIP_VEC_COSINE: i32 = 0;   // dbhip_vec_metric
 pub const DBHIP_VEC_L2: i32 = 1;   // dbhip_vec_metric
 pub const DBHIP_VEC_DOT: i32 = 2;   // dbhip_vec_metric
@@ -169,6 +175,7 @@ pub const DBHIP_REGEX_MAX_PATTERN: i32 = 1024;
 pub const DBHIP_REGEX_MAX_STATES: i32 = 4096;
 pub const DBHIP_REGEX_MAX_TABLE_BYTES: i32 = 32768;
 pub const DBHIP_CASE_MAX_CONDS: i32 = 16;
+pub const DBHIP_ARRAY_LONG_LEN: i32 = 32;
 
 #[repr(C)]
 pub struct dbhip_groupby { _private: [u8; 0] }
@@ -444,6 +451,13 @@ extern "C" {
     pub fn dbhip_str_split_part(col: *const dbhip_col, delim_host: *const u8, delim_len: i32, part: *const dbhip_col, n: i64, out_views: *mut c_void, stream: *mut c_void) -> i32;
     pub fn dbhip_str_rewrite_bytes(op: i32, col: *const dbhip_col, k: *const dbhip_col, x_host: *const u8, x_len: i32, y_host: *const u8, y_len: i32, flags: i32, n: i64, out_bytes_host: *mut u64, stream: *mut c_void) -> i32;
     pub fn dbhip_str_rewrite(op: i32, col: *const dbhip_col, k: *const dbhip_col, x_host: *const u8, x_len: i32, y_host: *const u8, y_len: i32, flags: i32, n: i64, out_views: *mut c_void, out_data: *mut u8, out_data_bytes: u64, err_count_dev: *mut u64, stream: *mut c_void) -> i32;
+    pub fn dbhip_array_length(offsets: *const u64, n: i64, n_elems: u64, out: *mut u64, bad_rows_dev: *mut u64, stream: *mut c_void) -> i32;
+    pub fn dbhip_array_get(elems: *const dbhip_col, offsets: *const u64, n: i64, n_elems: u64, index: *const dbhip_col, out_values: *mut c_void, out_validity: *mut u8, stream: *mut c_void) -> i32;
+    pub fn dbhip_array_find(op: i32, elems: *const dbhip_col, offsets: *const u64, n: i64, n_elems: u64, needle: *const dbhip_col, out: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn dbhip_array_find_str(op: i32, elems: *const dbhip_col, offsets: *const u64, n: i64, n_elems: u64, needle_host: *const u8, needle_len: i32, out: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn dbhip_array_reduce_result(kind: i32, elem_type: i32, precision: u8, scale: u8, out_type_host: *mut i32, out_precision_host: *mut u8, out_scale_host: *mut u8) -> i32;
+    pub fn dbhip_array_reduce(kind: i32, elems: *const dbhip_col, offsets: *const u64, n: i64, n_elems: u64, out: *mut c_void, out_validity: *mut u8, err_count_dev: *mut u64, stream: *mut c_void) -> i32;
+    pub fn dbhip_array_unnest_sel(offsets: *const u64, n: i64, n_elems: u64, out_sel: *mut u32, num_out: i64, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_distance_rows(metric: i32, elem_type: i32, lhs: *const c_void, lhs_is_scalar: i32, rhs: *const c_void, rhs_is_scalar: i32, n: i64, dim: i32, out: *mut c_void, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_distance(metric: i32, base: *const f32, n: i64, dim: i32, queries: *const f32, nq: i32, out: *mut f32, stream: *mut c_void) -> i32;
     pub fn dbhip_vec_topk(metric: i32, base: *const f32, n: i64, dim: i32, queries: *const f32, nq: i32, k: i32, out_idx: *mut u32, out_dist: *mut f32, stream: *mut c_void) -> i32;

@@ -135,6 +135,11 @@ STR_PARSE_MAX_BYTES = 256
 # dbhip_str_rewrite_op (the flag of the group is STR_UNIT_BYTE)
 STRW_REPLACE, STRW_LPAD, STRW_RPAD, STRW_REPEAT, STRW_REVERSE = range(5)
 
+# dbhip_array_reduce_kind, dbhip_array_find_op and the limits of the group (DBHIP_ARRAY_LONG_LEN; csrc/dev_array.h's stage and needle)
+ARR_COUNT, ARR_SUM, ARR_MIN, ARR_MAX = range(4)
+ARR_CONTAINS, ARR_INDEXOF = range(2)
+ARRAY_LONG_LEN, ARRAY_STAGE_BYTES, ARRAY_MAX_NEEDLE = 32, 8192, 255
+
 # dbhip_math_fn
 MATH_ABS, MATH_SIGN, MATH_CEIL, MATH_FLOOR, MATH_ROUND, MATH_TRUNCATE, MATH_SQRT = range(7)
 
@@ -170,7 +175,9 @@ SYMBOLS = [
     "dbhip_window_bounds", "dbhip_window_rank", "dbhip_window_shift", "dbhip_window_value", "dbhip_window_aggregate",
     "dbhip_like_kind", "dbhip_like", "dbhip_str_match", "dbhip_dt_part_type", "dbhip_dt_part", "dbhip_dt_trunc", "dbhip_dt_add", "dbhip_dt_diff", "dbhip_str_length", "dbhip_str_slice", "dbhip_str_build_bytes", "dbhip_str_build",
     "dbhip_inlist_create", "dbhip_inlist_path", "dbhip_inlist_eval", "dbhip_inlist_destroy", "dbhip_str_parse", "dbhip_str_format_bytes", "dbhip_str_format", "dbhip_regex_check", "dbhip_regex_create", "dbhip_regex_eval", "dbhip_regex_destroy", "dbhip_math_result", "dbhip_math", "dbhip_case_check", "dbhip_case", "dbhip_coalesce", "dbhip_bool_logic",
-    "dbhip_str_position", "dbhip_str_split_part", "dbhip_str_rewrite_bytes", "dbhip_str_rewrite", "dbhip_bitmap_set_indices", "dbhip_siphash64", "dbhip_scatter_indices", "dbhip_scatter_block", "dbhip_vec_distance", "dbhip_vec_distance_rows", "dbhip_vec_topk", "dbhip_score_u8",
+    "dbhip_str_position", "dbhip_str_split_part", "dbhip_str_rewrite_bytes", "dbhip_str_rewrite",
+    "dbhip_array_length", "dbhip_array_get", "dbhip_array_find", "dbhip_array_find_str", "dbhip_array_reduce_result", "dbhip_array_reduce", "dbhip_array_unnest_sel",
+    "dbhip_bitmap_set_indices", "dbhip_siphash64", "dbhip_scatter_indices", "dbhip_scatter_block", "dbhip_vec_distance", "dbhip_vec_distance_rows", "dbhip_vec_topk", "dbhip_score_u8",
     "dbhip_vec_topk_merge", "dbhip_vec_index_build", "dbhip_vec_index_search", "dbhip_vec_index_destroy",
     "dbhip_comm_unique_id", "dbhip_comm_create", "dbhip_comm_destroy", "dbhip_comm_abort", "dbhip_comm_allgather", "dbhip_comm_alltoall",
     "dbhip_comm_allreduce_sum_u64", "dbhip_groupby_exchange_allgather", "dbhip_groupby_exchange_alltoall", "dbhip_kmeans", "dbhip_vec_kernel_f32", "dbhip_hnsw_build", "dbhip_hnsw_build_sequential", "dbhip_hnsw_from_graph", "dbhip_hnsw_open", "dbhip_hnsw_export_graph", "dbhip_hnsw_search", "dbhip_hnsw_scores",
@@ -245,6 +252,17 @@ def load_library():
     L.dbhip_str_rewrite_bytes.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
     L.dbhip_str_rewrite.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                     C.c_uint64, C.c_void_p, C.c_void_p]
+    # the Array group: (offsets, n, n_elems, out, bad_rows, stream) / (elems, offsets, n, n_elems, index, out_values, out_validity, stream) /
+    # (op, elems, offsets, n, n_elems, needle, out, stream) / (op, elems, offsets, n, n_elems, needle, len, out, stream) /
+    # (kind, elem_type, precision, scale, out_type, out_precision, out_scale) / (kind, elems, offsets, n, n_elems, out, out_validity,
+    # err_count, stream) / (offsets, n, n_elems, out_sel, num_out, stream)
+    L.dbhip_array_length.argtypes = [C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.dbhip_array_get.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.dbhip_array_find.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.dbhip_array_find_str.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.dbhip_array_reduce_result.argtypes = [C.c_int32, C.c_int32, C.c_uint8, C.c_uint8, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.dbhip_array_reduce.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.dbhip_array_unnest_sel.argtypes = [C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p, C.c_int64, C.c_void_p]
     # the math group: (fn, src_type, src_precision, src_scale, digits, out_type, out_precision, out_scale) / (fn, src, digits, n, out, stream)
     L.dbhip_math_result.argtypes = [C.c_int32, C.c_int32, C.c_uint8, C.c_uint8, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.dbhip_math.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]

@@ -40,7 +40,7 @@ struct Scratch {
 //     so a host that takes a fresh stream per query — or torch's stream pool — cannot grow device memory without bound, and a
 //     recycled hipStream_t value never inherits more than that.
 struct StreamScratch {
-  Scratch slot[28];   // (0 .. 27: the highest one is k_strsearch.hip's)
+  Scratch slot[29];   // (0 .. 28: the highest one is k_array.hip's)
   uint64_t last_use = 0;
 };
 constexpr size_t SCRATCH_STREAMS_PER_THREAD = 8;

@@ -889,6 +889,186 @@ def reverse(col, unit_byte=False, n=None):
     return _str_rewrite(L.STRW_REVERSE, col, unit_byte=unit_byte, n=n)
 
 
+class ArrayColumn:
+    """Databend's ArrayColumn on the device: `offsets` (n + 1 u64 that index the child directly), the child Column with the elements of
+    all rows back to back, and an optional validity Bitmap for the rows (a Nullable(Array(T))), read from bit `voff`."""
+
+    def __init__(self, offsets, n, child, validity=None, voff=0, keep=()):
+        self.offsets, self.n, self.child, self.validity, self.voff, self._keep = offsets, int(n), child, validity, int(voff), keep
+
+    @classmethod
+    def from_lists(cls, lists, dtype, precision=0, scale=0):
+        """lists: per row a list of values (None = a NULL element) or None (a NULL row, stored as an empty run)"""
+        offsets, vals, ev, rv = [0], [], [], []
+        for row in lists:
+            rv.append(row is not None)
+            for x in row or ():
+                ev.append(x is not None)
+                vals.append(x)
+            offsets.append(len(vals))
+        ev = None if all(ev) else ev
+        if dtype == L.T_STRING:
+            child = Column.strings([x if x is not None else b"" for x in vals], ev)
+        elif dtype == L.T_DEC128:
+            child = Column.decimal128([x if x is not None else 0 for x in vals], precision, scale, ev)
+        else:
+            child = Column.from_numpy(np.array([x if x is not None else 0 for x in vals], dtype=NP_OF[dtype]), dtype, ev, precision, scale)
+        vb = None if all(rv) else DeviceBuffer.from_numpy(pack_bits(rv))
+        return cls(DeviceBuffer.from_numpy(np.array(offsets, dtype=np.uint64)), len(lists), child, vb)
+
+    def slice(self, lo, hi):
+        """rows [lo, hi) as a view: the offsets by address (they keep indexing the whole child), the Bitmap by bit offset"""
+        assert 0 <= lo <= hi <= self.n
+        off = BorrowedBuffer(self.offsets.ptr + lo * 8, (hi - lo + 1) * 8, keep=self.offsets)
+        return ArrayColumn(off, hi - lo, self.child, self.validity, self.voff + lo, keep=(self,))
+
+    def offsets_numpy(self):
+        return self.offsets.to_numpy(np.uint64, self.n + 1)
+
+    def validity_numpy(self):
+        if self.validity is None:
+            return np.ones(self.n, dtype=bool)
+        return unpack_bits(self.validity.to_numpy(np.uint8, (self.voff + self.n + 7) // 8), self.voff + self.n)[self.voff:]
+
+    def to_lists(self):
+        off = [int(x) for x in self.offsets_numpy()]
+        c = self.child
+        vals = c.string_values() if c.dtype == L.T_STRING else c.to_numpy()
+        vals = vals.tolist() if isinstance(vals, np.ndarray) else list(vals)
+        ev = c.validity_numpy()
+        rows = [[vals[e] if ev[e] else None for e in range(off[r], off[r + 1])] for r in range(self.n)]
+        return [row if ok else None for row, ok in zip(rows, self.validity_numpy())]
+
+
+def _array_result(arr, col, own=None):
+    """a result Column of an Array function: the function's own validity Bitmap (at bit 0, or None) AND the Array column's"""
+    n = arr.n
+    if own is None:
+        col.validity, col.voff = arr.validity, arr.voff
+    elif arr.validity is None:
+        col.validity, col.voff = own, 0
+    else:
+        rows = _bits_at_zero(arr.validity, arr.voff, n)
+        out = DeviceBuffer(((n + 63) // 64) * 8 + 8)
+        check(lib().dbhip_bitmap_binary(0, C.c_void_p(own.ptr), C.c_void_p(rows.ptr), C.c_int64(n), C.c_void_p(out.ptr), None))
+        col.validity, col.voff = out, 0
+    col._keep = tuple(col._keep) + (arr,)
+    return col
+
+
+def _array_args(arr):
+    cc = arr.child.c()
+    return cc, C.byref(cc), C.c_void_p(arr.offsets.ptr), C.c_int64(arr.n), C.c_uint64(arr.child.n)
+
+
+def array_length(arr, want_bad_rows=False):
+    """length(arr) / array_length (dbhip_array_length) -> UInt64 Column with the Array column's validity (and, on request, the number
+    of rows whose offsets decrease or end past the child: they count 0)"""
+    out = DeviceBuffer(max(arr.n, 1) * 8)
+    bad = DeviceBuffer(8).zero()
+    check(lib().dbhip_array_length(C.c_void_p(arr.offsets.ptr), C.c_int64(arr.n), C.c_uint64(arr.child.n), C.c_void_p(out.ptr), C.c_void_p(bad.ptr), None))
+    res = _array_result(arr, Column(L.T_U64, arr.n, out))
+    return (res, int(bad.to_numpy(np.uint64, 1)[0])) if want_bad_rows else res
+
+
+def array_get(arr, index):
+    """get(arr, i) / arr[i] (dbhip_array_get): 1-based, a negative index from the end, NULL outside the run; `index` is a Python int or
+    an Int64 Column -> Column of the child's type (a String result shares the child's buffer table)"""
+    index = _i64_arg(index)
+    c = arr.child
+    out = DeviceBuffer(max(arr.n, 1) * ELEM_SIZE[c.dtype] + 64)
+    vb = DeviceBuffer(((arr.n + 63) // 64) * 8 + 8)
+    _, cref, off, n, ne = _array_args(arr)
+    ci = index.c()
+    check(lib().dbhip_array_get(cref, off, n, ne, C.byref(ci), C.c_void_p(out.ptr), C.c_void_p(vb.ptr), None))
+    res = Column(c.dtype, arr.n, out, None, c.precision, c.scale, buffers=c.buffers, keep=(c, index))
+    res.n_buffers = c.n_buffers
+    return _array_result(arr, res, vb)
+
+
+def _array_find(op, arr, needle):
+    _, cref, off, n, ne = _array_args(arr)
+    out = DeviceBuffer(((arr.n + 63) // 64) * 8 + 8 if op == L.ARR_CONTAINS else max(arr.n, 1) * 8)
+    keep = ()
+    if arr.child.dtype == L.T_STRING:
+        buf, ln = _host_bytes(needle)
+        check(lib().dbhip_array_find_str(C.c_int32(op), cref, off, n, ne, buf, C.c_int32(ln), C.c_void_p(out.ptr), None))
+    else:
+        if not isinstance(needle, Column):
+            needle = Column.scalar(needle, arr.child.dtype, arr.child.precision, arr.child.scale)
+        cn = needle.c()
+        check(lib().dbhip_array_find(C.c_int32(op), cref, off, n, ne, C.byref(cn), C.c_void_p(out.ptr), None))
+        keep = (needle,)
+    return _array_result(arr, Column(L.T_BOOL if op == L.ARR_CONTAINS else L.T_U64, arr.n, out, keep=keep))
+
+
+def array_contains(arr, needle):
+    """contains(arr, x) (dbhip_array_find / _find_str): x is a Python value, a Column of the elements' type, or bytes for a String child
+    -> Boolean Column; a NULL element never matches, a NULL needle row gives false"""
+    return _array_find(L.ARR_CONTAINS, arr, needle)
+
+
+def array_indexof(arr, needle):
+    """array_indexof(arr, x): the 1-based position of the first equal element, 0 when there is none -> UInt64 Column"""
+    return _array_find(L.ARR_INDEXOF, arr, needle)
+
+
+def array_reduce_result(kind, col):
+    """dbhip_array_reduce_result: (result type, precision, scale) of L.ARR_* over the child `col`; raises where it is not offered"""
+    t, p, s = C.c_int32(0), C.c_uint8(0), C.c_uint8(0)
+    check(lib().dbhip_array_reduce_result(C.c_int32(kind), C.c_int32(col.dtype), C.c_uint8(col.precision), C.c_uint8(col.scale), C.byref(t), C.byref(p), C.byref(s)))
+    return t.value, p.value, s.value
+
+
+def _array_reduce(kind, arr):
+    t, p, s = array_reduce_result(kind, arr.child)
+    out = DeviceBuffer(max(arr.n, 1) * ELEM_SIZE[t] + 64)
+    vb = DeviceBuffer(((arr.n + 63) // 64) * 8 + 8)
+    errs = DeviceBuffer(8).zero()
+    _, cref, off, n, ne = _array_args(arr)
+    check(lib().dbhip_array_reduce(C.c_int32(kind), cref, off, n, ne, C.c_void_p(out.ptr), C.c_void_p(vb.ptr), C.c_void_p(errs.ptr), None))
+    res = _array_result(arr, Column(t, arr.n, out, None, p, s), None if kind == L.ARR_COUNT else vb)
+    res.array_errors = errs                     # one u64: the Decimal128 sums that left the decimal range (those rows are NULL)
+    return res
+
+
+def array_count(arr):
+    """array_count(arr): the non-NULL elements -> UInt64 Column"""
+    return _array_reduce(L.ARR_COUNT, arr)
+
+
+def array_sum(arr):
+    """array_sum(arr): NULL for an empty run or a run of NULLs (coalesce where 0 is wanted); the type is dbhip_groupby_result_type's"""
+    return _array_reduce(L.ARR_SUM, arr)
+
+
+def array_min(arr):
+    return _array_reduce(L.ARR_MIN, arr)
+
+
+def array_max(arr):
+    return _array_reduce(L.ARR_MAX, arr)
+
+
+def array_avg(arr):
+    """array_avg(arr) over a number child: array_sum / array_count as Float64 (dbhip_arith's divnull: a run without a value is NULL)"""
+    s, c = array_sum(arr), array_count(arr)
+    return arith(L.OP_DIVNULL, s, c, n=arr.n, errors=RowErrors(arr.n))      # a zero count divides a NULL sum: the merged validity says so
+
+
+def unnest(arr):
+    """UNNEST(arr) -> (sel, k, values): the parent-row selection (a DeviceBuffer of k u32 for take / take_block over the sibling
+    columns) and the child's slice that holds the k unnested values"""
+    lo = hi = 0
+    if arr.n:                                   # the run's two ends, 16 bytes: the caller of the C entry usually knows them already
+        lo = int(BorrowedBuffer(arr.offsets.ptr, 8).to_numpy(np.uint64, 1)[0])
+        hi = int(BorrowedBuffer(arr.offsets.ptr + arr.n * 8, 8).to_numpy(np.uint64, 1)[0])
+    k = max(hi - lo, 0)
+    sel = DeviceBuffer(max(k, 1) * 4 + 64)
+    check(lib().dbhip_array_unnest_sel(C.c_void_p(arr.offsets.ptr), C.c_int64(arr.n), C.c_uint64(arr.child.n), C.c_void_p(sel.ptr), C.c_int64(k), None))
+    return sel, k, arr.child.slice(lo, lo + k)
+
+
 def parse_strings(col, dtype, precision=0, scale=0, is_try=False, rounding_mode=False, offset_s=0, n=None, errors=None):
     """to_int8 .. to_uint64 / to_decimal(p, s) / to_date / to_timestamp and their try_ forms on a String column (dbhip_str_parse) ->
     (Column, declined): `declined` is the number of rows the device did not decide (they hold 0): when it is not zero the caller
@@ -2867,6 +3047,7 @@ class ParquetChunk:
                                                       C.c_void_p(offs.ptr), C.c_void_p(lval.ptr) if lval is not None else None, C.c_void_p(out.ptr),
                                                       C.c_void_p(eval_.ptr) if eval_ is not None else None, C.byref(rows), C.byref(elems), C.byref(nl), stream))
         self.rows, self.elems, self.null_lists = rows.value, elems.value, nl.value
+        self.offsets_dev, self.list_validity_dev = offs, lval       # what ArrayColumn takes as they are
         buf0 = self.image_dev if self.image_dev is not None else chunk_dev
         bufs, keep = self._string_buffers(buf0) if self.out_type == L.T_STRING else (None, (buf0,))
         col = Column(self.out_type, elems.value, out, eval_, self.precision, self.scale, buffers=bufs, keep=keep)

@@ -41,7 +41,7 @@ extern "C" {
 #endif
 
 #define DBHIP_ABI_VERSION 6   /* 6 (round 6): pipelined fused aggregation (dbhip_groupby_set_pipelined / dbhip_groupby_checkpoint), and (backward
-                                 compatible, same version) DELTA_(LENGTH_)BYTE_ARRAY / BYTE_STREAM_SPLIT on the device with dbhip_pq_chunk_take_arena; likewise the Date / Timestamp functions (a21: dbhip_dt_part / _trunc / _add / _diff, DBHIP_EX_DT_PART / DBHIP_EX_DT_TRUNC), the math functions (a26: dbhip_math_result / dbhip_math) the conditionals (a27: dbhip_case_check / dbhip_case / dbhip_coalesce / dbhip_bool_logic) and String search and rewrite (a28: dbhip_str_position / dbhip_str_split_part / dbhip_str_rewrite_bytes / dbhip_str_rewrite; 200 functions in all); 5 (round 5): ZSTD on the device, batched chunk decode (dbhip_pq_chunks_decode_device); 4 (round 4): block scatter / concat, exchange and plan calls, device-mode scan, cancellation, row-wise vector distance */
+                                 compatible, same version) DELTA_(LENGTH_)BYTE_ARRAY / BYTE_STREAM_SPLIT on the device with dbhip_pq_chunk_take_arena; likewise the Date / Timestamp functions (a21: dbhip_dt_part / _trunc / _add / _diff, DBHIP_EX_DT_PART / DBHIP_EX_DT_TRUNC), the math functions (a26: dbhip_math_result / dbhip_math) the conditionals (a27: dbhip_case_check / dbhip_case / dbhip_coalesce / dbhip_bool_logic) String search and rewrite (a28: dbhip_str_position / dbhip_str_split_part / dbhip_str_rewrite_bytes / dbhip_str_rewrite) and the Array functions (a29: dbhip_array_length / _get / _find / _find_str / _reduce_result / _reduce / _unnest_sel; 207 functions in all); 5 (round 5): ZSTD on the device, batched chunk decode (dbhip_pq_chunks_decode_device); 4 (round 4): block scatter / concat, exchange and plan calls, device-mode scan, cancellation, row-wise vector distance */
 
 /* ---- status codes ------------------------------------------------------- */
 enum {
@@ -1470,6 +1470,86 @@ int32_t dbhip_str_rewrite_bytes(int32_t op, const dbhip_col* col, const dbhip_co
 int32_t dbhip_str_rewrite(int32_t op, const dbhip_col* col, const dbhip_col* k, const uint8_t* x_host, int32_t x_len,
                           const uint8_t* y_host, int32_t y_len, int32_t flags, int64_t n, void* out_views, uint8_t* out_data,
                           uint64_t out_data_bytes, uint64_t* err_count_dev, void* stream);
+/* jit-embed: resume */
+
+/* jit-embed: skip (as a19: the run-time compiled kernels never see this group; the codes and limits the kernels use are restated in csrc/dev_array.h) */
+/* ---- a29: Array functions: length, get, contains / indexof, count / sum / min / max, the unnest selection ----------
+ * Replaces the closures behind length / array_length, get / arr[i], contains, array_indexof, array_count, array_sum, array_min,
+ * array_max (array_avg is a composition in the binding) and the parent-row side of UNNEST (INTEGRATION.md §24 maps the names), over
+ * the ArrayColumn layout the scan decodes (dbhip_pq_chunk_decode_device_list / _nested). The reference's source is not at hand, so
+ * this comment is the definition; csrc/dev_array.h implements the row logic once, for the kernels and for the host checker
+ * (tests/array_host_check.cpp).
+ *
+ * Column. `offsets`: n + 1 device u64, 8-byte aligned, Databend's ArrayColumn offsets: row r owns the elements offsets[r] ..
+ * offsets[r + 1]. They index the child directly: a sliced column (offsets[0] > 0) needs no rebasing. `elems`: the child, the values
+ * of all rows back to back, n_elems of them; is_scalar must be 0, else DBHIP_ERR_INVALID; its data is aligned to the element's size
+ * (16 bytes for Decimal128 and String views); its validity bit for element e is bit validity_offset + e, a NULL validity means every
+ * element is valid. With n_elems = 0 the data pointer is not looked at. A BAD ROW, offsets[r] > offsets[r + 1] or offsets[r + 1] >
+ * n_elems, is never dereferenced and behaves as an empty array in every function; nothing on the device faults on a malformed
+ * offsets buffer. There is no list-validity argument and, except where stated, no result validity for the row: the binding merges
+ * the Array column's own Bitmap, as for a22 and a28; the run of a NULL row is processed like any other. n = 0 returns DBHIP_OK before
+ * any launch; n > 2^32 - 2 is DBHIP_ERR_INVALID. BOOL and DEC256 elements are DBHIP_ERR_UNSUPPORTED before any launch (keep the CPU
+ * closure); any other pair of function and element type that is not listed below is DBHIP_ERR_INVALID. The stream stays usable after
+ * every refusal. With len = offsets[r + 1] - offsets[r]:
+ *
+ * dbhip_array_length: out[r] = len (n u64, 8-byte aligned); a bad row gives 0 and is added to *bad_rows_dev (may be NULL; 8-byte
+ * aligned; the caller zeroes it).
+ *
+ * dbhip_array_get: arr[i] with i = index[r] (a DBHIP_T_I64 column or scalar whose validity is not read). 1 <= i <= len takes element i
+ * (1-based); -len <= i <= -1 takes element len + i + 1; anything else (0, a value beyond the run either way, INT64_MIN, INT64_MAX)
+ * gives the zero value with validity bit 0, decided by comparisons before any arithmetic. Elements move uninterpreted: sizes 1, 2, 4,
+ * 8, 16, that is the ten number types, DATE, TIMESTAMP, DEC64, DEC128 and STRING views. out_values: n elements, aligned to their size.
+ * out_validity is required: LSB-first, 8-byte aligned, ceil(n/64)*8 bytes, whole words written; bit = in range AND the element's
+ * validity bit. An inline String result is copied as stored, a long view is copied whole: the result shares the child's buffer table.
+ *
+ * dbhip_array_find / dbhip_array_find_str: DBHIP_ARR_CONTAINS writes a Bitmap `out` (LSB-first, 8-byte aligned, ceil(n/64)*8 bytes,
+ * whole words written); DBHIP_ARR_INDEXOF writes n u64: the 1-based position of the FIRST equal element, or 0. A NULL element never
+ * matches. _find takes the ten number types, DATE, TIMESTAMP, DEC64 and DEC128; `needle` is a column or a scalar of the elements' type,
+ * and for decimals of their precision and scale, else DBHIP_ERR_INVALID; a NULL needle row (its validity bit 0) gives 0 / false.
+ * Equality is dbhip_cmp(EQ)'s: integers and decimals exact; floats as OrderedFloat, NaN equal to NaN whatever the sign or payload,
+ * -0.0 equal to 0.0. _find_str takes STRING elements and host bytes of length 0..255: more is DBHIP_ERR_UNSUPPORTED; a negative length,
+ * or a NULL pointer with a positive length, is DBHIP_ERR_INVALID. Its equality is bytewise, decided by length, then by the view's
+ * prefix, then by the bytes; a28's read rule holds (only loads inside the value's own aligned 4-byte words; the bytes of an inline
+ * view past its length are not looked at); a long view that names a buffer >= n_buffers or a NULL table entry is never dereferenced
+ * and does not match.
+ *
+ * dbhip_array_reduce: NULL elements are skipped. COUNT: the number of non-NULL elements as u64; out_validity (may be NULL for COUNT
+ * only) is all ones for the n rows. SUM / MIN / MAX over an empty run or a run of NULLs: value 0 with validity bit 0 (the binding
+ * coalesces where the reference wants 0). SUM takes the ten number types, DEC64 and DEC128; MIN, MAX and COUNT also DATE and TIMESTAMP.
+ * `out` has exactly the type dbhip_groupby_result_type gives for the same kind and argument, which dbhip_array_reduce_result returns
+ * (a host function; the out pointers for precision and scale may be NULL): COUNT u64; SUM of signed integers i64 and of unsigned
+ * u64, both wrapping; of floats f64, a sum of doubles in an unspecified order and tree; of DEC64 DEC64(18, s), wrapping; of DEC128
+ * DEC128(38, s): the exact sum, and a sum outside +-(10^38 - 1) gives value 0 with validity 0 and is added to *err_count_dev (may be
+ * NULL; 8-byte aligned; the caller zeroes it); MIN / MAX have the elements' type, floats in OrderedFloat's total order with NaN
+ * greatest (among NaNs, and among -0.0 and 0.0, either may come back). out_validity: as for get.
+ *
+ * dbhip_array_unnest_sel: the parent-row selection for dbhip_take / dbhip_take_block over the sibling columns; the unnested values
+ * themselves are the child's slice offsets[0] .. offsets[n]. out_sel[k] = r for offsets[r] - offsets[0] <= k < offsets[r + 1] -
+ * offsets[0]; empty arrays vanish. num_out is the caller's offsets[n] - offsets[0] (the scan and the binding know it); only slots
+ * k < num_out are written, whatever the offsets say.
+ *
+ * Calls. Asynchronous on `stream`; scratch comes from the (thread, stream) scratch; cancellation is polled between the launches. No
+ * lane folds or searches more than DBHIP_ARRAY_LONG_LEN elements of one row: a longer row goes through a row list in scratch (4 bytes
+ * per row of the call) to a wave-per-row pass that reads the list's length on the device and takes 64 elements per step.
+ * Out of scope: slice, array_concat, array_distinct, array_sort, array_flatten, range (they build new offsets); array_filter and
+ * array_transform (lambdas); BOOL and Decimal256 elements; a String needle that is a column; nested arrays as elements; Map functions;
+ * ops inside dbhip_expr_eval programs; the C++ host mirror and the Rust shim (which wrap none of a21 - a28 either). */
+#define DBHIP_ARRAY_LONG_LEN 32
+typedef enum { DBHIP_ARR_COUNT = 0, DBHIP_ARR_SUM = 1, DBHIP_ARR_MIN = 2, DBHIP_ARR_MAX = 3 } dbhip_array_reduce_kind;
+typedef enum { DBHIP_ARR_CONTAINS = 0, DBHIP_ARR_INDEXOF = 1 } dbhip_array_find_op;
+
+int32_t dbhip_array_length(const uint64_t* offsets, int64_t n, uint64_t n_elems, uint64_t* out, uint64_t* bad_rows_dev, void* stream);
+int32_t dbhip_array_get(const dbhip_col* elems, const uint64_t* offsets, int64_t n, uint64_t n_elems,
+                        const dbhip_col* index /* I64 column or scalar */, void* out_values, uint8_t* out_validity, void* stream);
+int32_t dbhip_array_find(int32_t op, const dbhip_col* elems, const uint64_t* offsets, int64_t n, uint64_t n_elems,
+                         const dbhip_col* needle /* the elements' type; column or scalar */, void* out, void* stream);
+int32_t dbhip_array_find_str(int32_t op, const dbhip_col* elems, const uint64_t* offsets, int64_t n, uint64_t n_elems,
+                             const uint8_t* needle_host, int32_t needle_len, void* out, void* stream);
+int32_t dbhip_array_reduce_result(int32_t kind, int32_t elem_type, uint8_t precision, uint8_t scale, int32_t* out_type_host,
+                                  uint8_t* out_precision_host, uint8_t* out_scale_host);
+int32_t dbhip_array_reduce(int32_t kind, const dbhip_col* elems, const uint64_t* offsets, int64_t n, uint64_t n_elems, void* out,
+                           uint8_t* out_validity, uint64_t* err_count_dev, void* stream);
+int32_t dbhip_array_unnest_sel(const uint64_t* offsets, int64_t n, uint64_t n_elems, uint32_t* out_sel, int64_t num_out, void* stream);
 /* jit-embed: resume */
 
 /* ---- a17/a18: vector distance ------------------------------------------------
