@@ -17,7 +17,6 @@ constexpr uint32_t AR_LONG_LEN = 32;
 constexpr uint32_t AR_WAVE_STEP = 64;
 constexpr uint32_t AR_STAGE_BYTES = 8192;
 constexpr int AR_MAX_NEEDLE = 255;
-constexpr int64_t AR_MAX_ROWS = 0xFFFFFFFELL;
 
 typedef __int128 ar_i128;
 typedef unsigned __int128 ar_u128;

@@ -7,9 +7,9 @@
 //            cursor c0, stages the child's bytes from c0 on (AR_STAGE_BYTES, from the 16-byte boundary at or below c0, 16-byte loads
 //            wherever the 16 bytes lie inside the child) and the validity bits that go with them in LDS, and every lane folds or
 //            searches the part of its run that lies in the stage, out of LDS. The lane with the smallest cursor advances, so the
-//            loop ends. A row of more than AR_LONG_LEN elements is not touched: its id goes into a list in scratch (one ballot and one
-//            atomic add per wave) and its output is written as zero.
-//   long rows   one wave per listed row on a fixed grid, the list's length read on the device, AR_WAVE_STEP elements per step loaded
+//            loop ends. A row of more than AR_LONG_LEN elements is not touched: its id goes into the long-row list (dev_longrows.h)
+//            and its output is written as zero.
+//   long rows   one wave per listed row (dev_longrows.h), AR_WAVE_STEP elements per step loaded
 //            straight from the child (neighbouring lanes, neighbouring elements); the parts are folded with shuffles, the first match is
 //            the lowest bit of a ballot.
 //   get and length are maps with one lane per row; unnest_sel stages ROW IDS in LDS the same way (a lane writes its run's slots, the
@@ -19,6 +19,7 @@
 #include <string.h>
 #include "dev_common.h"
 #include "dev_array.h"
+#include "dev_longrows.h"
 #include "runtime.h"
 
 using namespace dbhip;
@@ -35,7 +36,6 @@ static_assert(AR_LONG_LEN == DBHIP_ARRAY_LONG_LEN && AR_WAVE_STEP == DBHIP_WAVE 
 namespace {
 
 constexpr int AR_SCRATCH_SLOT = 28;
-constexpr int AR_PASS2_BLOCKS = 512;           // fixed grid of the wave-per-row passes: 2,048 waves that stride over the list
 constexpr uint32_t AR_NO_ROW = 0xFFFFFFFFu;    // an empty slot of unnest's stage (a row id is at most 2^32 - 3)
 constexpr uint32_t AR_STAGE_SLOTS = AR_STAGE_BYTES / 4;
 constexpr int AR_LONG_UNROLL = 4;              // steps of the wave-per-row pass whose loads are issued together
@@ -56,15 +56,13 @@ struct ArParams {
   void* out;
   unsigned long long* out_words;     // the validity / CONTAINS Bitmap, as words
   unsigned long long* err_count;
-  uint32_t* long_count;
-  uint32_t* long_rows;
+  LongList list;
   uint32_t* out_sel;
   uint64_t num_out;
   uint32_t nd_len, _pad;
   uint8_t nd[256];                   // find_str: the needle's bytes
 };
 
-__device__ __forceinline__ uint64_t lanes_below(uint32_t lane) { return (1ull << lane) - 1ull; }
 __device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) {
@@ -86,16 +84,6 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-// one ballot and one atomic add per wave: the listed lanes' rows go into the list
-__device__ __forceinline__ void list_rows(bool listed, uint32_t lane, int64_t i, uint32_t* long_count, uint32_t* long_rows) {
-  const uint64_t lmask = __ballot(listed);
-  if (lmask) {                                // wave-uniform
-    uint32_t at = 0;
-    if (lane == 0) at = atomicAdd(long_count, (uint32_t)__popcll(lmask));
-    at = __shfl(at, 0, 64);
-    if (listed) long_rows[at + (uint32_t)__popcll(lmask & lanes_below(lane))] = (uint32_t)i;
-  }
 }
 __device__ __forceinline__ bool elem_valid(const ArParams& P, uint64_t e) { return !P.validity || bit_get(P.validity, P.voff + (int64_t)e); }
 
@@ -189,7 +177,7 @@ __global__ __launch_bounds__(256) void ar_reduce_kernel(const ArParams P) {
     if (i < P.n) ar_store(P.out, (uint64_t)i, P.out_es, r);
     const uint64_t word = __ballot(ok);
     if (lane == 0 && P.out_words) P.out_words[wave0 >> 6] = word;
-    list_rows(listed, lane, i, P.long_count, P.long_rows);
+    list_rows(listed, lane, i, P.list);
   }
   errs = (uint32_t)wave_sum_u64(errs);                       // every lane arrives here: one add per wave
   if (lane == 0 && errs && P.err_count) atomicAdd(P.err_count, (unsigned long long)errs);
@@ -197,10 +185,9 @@ __global__ __launch_bounds__(256) void ar_reduce_kernel(const ArParams P) {
 template <int CLS>
 __global__ __launch_bounds__(256) void ar_reduce_long_kernel(const ArParams P) {
   const uint32_t lane = threadIdx.x & 63;
-  const uint32_t count = *P.long_count;
-  const uint32_t nwaves = gridDim.x * 4;
-  for (uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6); q < count; q += nwaves) {
-    const int64_t i = P.long_rows[q];
+  const LongWalk lw = long_walk(P.list);
+  for (uint32_t q = lw.first; q < lw.count; q += lw.stride) {
+    const int64_t i = P.list.rows[q];
     uint64_t start, len;
     ar_row(P.offsets, i, P.n_elems, &start, &len);           // pass 1 found it good and long
     ArAcc acc;
@@ -305,7 +292,7 @@ __global__ __launch_bounds__(256) void ar_find_kernel(const ArParams P) {
     } else if (i < P.n) {
       ((uint64_t*)P.out)[i] = pos;
     }
-    list_rows(listed, lane, i, P.long_count, P.long_rows);
+    list_rows(listed, lane, i, P.list);
   }
 }
 template <bool STR>
@@ -313,10 +300,9 @@ __global__ __launch_bounds__(256) void ar_find_long_kernel(const ArParams P) {
   __shared__ uint8_t nd_bytes[256];
   if (STR) needle_stage(P, nd_bytes);
   const uint32_t lane = threadIdx.x & 63;
-  const uint32_t count = *P.long_count;
-  const uint32_t nwaves = gridDim.x * 4;
-  for (uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6); q < count; q += nwaves) {
-    const int64_t i = P.long_rows[q];
+  const LongWalk lw = long_walk(P.list);
+  for (uint32_t q = lw.first; q < lw.count; q += lw.stride) {
+    const int64_t i = P.list.rows[q];
     uint64_t start, len, pos = 0;
     ar_row(P.offsets, i, P.n_elems, &start, &len);           // pass 1 found it good and long, and its needle not NULL
     ArBits nd{0, 0};
@@ -378,16 +364,15 @@ __global__ __launch_bounds__(256) void ar_unnest_kernel(const ArParams P) {
       }
       wave_lds_sync();                                       // the stage is rewritten by the next round
     }
-    list_rows(listed, lane, i, P.long_count, P.long_rows);
+    list_rows(listed, lane, i, P.list);
   }
 }
 __global__ __launch_bounds__(256) void ar_unnest_long_kernel(const ArParams P) {
   const uint32_t lane = threadIdx.x & 63;
-  const uint32_t count = *P.long_count;
-  const uint32_t nwaves = gridDim.x * 4;
+  const LongWalk lw = long_walk(P.list);
   const uint64_t o0 = P.offsets[0];
-  for (uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6); q < count; q += nwaves) {
-    const int64_t i = P.long_rows[q];
+  for (uint32_t q = lw.first; q < lw.count; q += lw.stride) {
+    const int64_t i = P.list.rows[q];
     uint64_t start, len;
     ar_row(P.offsets, i, P.n_elems, &start, &len);
     if (start < o0) continue;
@@ -433,7 +418,7 @@ __global__ __launch_bounds__(256) void ar_get_kernel(const ArParams P, const int
 // ---- the host side ---------------------------------------------------------------------------------------------------------------------------
 // what every call checks. *done: the call is over (n = 0) with the returned status.
 int32_t check_array(const uint64_t* offsets, int64_t n, const dbhip_col* elems, uint64_t n_elems, bool need_elems, const char* who) {
-  if (n < 0 || n > AR_MAX_ROWS) { set_error("%s: row count outside 0 .. 2^32 - 2", who); return DBHIP_ERR_INVALID; }
+  if (n < 0 || n > LONGROWS_MAX_ROWS) { set_error("%s: row count outside 0 .. 2^32 - 2", who); return DBHIP_ERR_INVALID; }
   if (n > 0 && (!offsets || ((uintptr_t)offsets & 7))) { set_error("%s: NULL offsets or offsets not 8-byte aligned", who); return DBHIP_ERR_INVALID; }
   if (!need_elems) return DBHIP_OK;
   if (!elems) { set_error("%s: NULL elems", who); return DBHIP_ERR_INVALID; }
@@ -465,21 +450,6 @@ void base_params(ArParams& P, const dbhip_col* elems, const uint64_t* offsets, i
     P.es = ar_size(elems->type);
     P.mode = ar_eq_mode(elems->type);
   }
-}
-// pass 1 and the wave-per-row pass over its list
-template <class K1, class K2>
-int32_t two_passes(ArParams& P, K1 rows_kernel, K2 long_kernel, hipStream_t s, const char* who) {
-  uint8_t* ws = (uint8_t*)scratch(64 + (size_t)P.n * 4 + 64, AR_SCRATCH_SLOT, s);
-  if (!ws) return DBHIP_ERR_HIP;
-  P.long_count = (uint32_t*)ws;
-  P.long_rows = (uint32_t*)(ws + 64);
-  DBHIP_CHECK(hipMemsetAsync(ws, 0, 16, s));
-  hipLaunchKernelGGL(rows_kernel, dim3(grid_for(P.n, 256)), dim3(256), 0, s, P);
-  DBHIP_LAUNCH_CHECK();
-  DBHIP_POLL_CANCEL(s, who);
-  hipLaunchKernelGGL(long_kernel, dim3(AR_PASS2_BLOCKS), dim3(256), 0, s, P);
-  DBHIP_LAUNCH_CHECK();
-  return DBHIP_OK;
 }
 int32_t check_find(int32_t op, void* out, const char* who) {
   if (!out || ((uintptr_t)out & 7)) { set_error("%s: NULL out or out not 8-byte aligned", who); return DBHIP_ERR_INVALID; }
@@ -551,7 +521,7 @@ int32_t dbhip_array_find(int32_t op, const dbhip_col* elems, const uint64_t* off
   P.nd_scalar = needle->is_scalar ? 1 : 0;
   P.out = out;
   P.out_words = (unsigned long long*)out;
-  return two_passes(P, ar_find_kernel<false>, ar_find_long_kernel<false>, s, who);
+  return long_two_passes(P, ar_find_kernel<false>, ar_find_long_kernel<false>, AR_SCRATCH_SLOT, s, who);
 }
 
 int32_t dbhip_array_find_str(int32_t op, const dbhip_col* elems, const uint64_t* offsets, int64_t n, uint64_t n_elems, const uint8_t* needle_host,
@@ -573,7 +543,7 @@ int32_t dbhip_array_find_str(int32_t op, const dbhip_col* elems, const uint64_t*
   if (needle_len) memcpy(P.nd, needle_host, (size_t)needle_len);
   P.out = out;
   P.out_words = (unsigned long long*)out;
-  return two_passes(P, ar_find_kernel<true>, ar_find_long_kernel<true>, s, who);
+  return long_two_passes(P, ar_find_kernel<true>, ar_find_long_kernel<true>, AR_SCRATCH_SLOT, s, who);
 }
 
 int32_t dbhip_array_reduce_result(int32_t kind, int32_t elem_type, uint8_t precision, uint8_t scale, int32_t* out_type_host, uint8_t* out_precision_host,
@@ -614,11 +584,11 @@ int32_t dbhip_array_reduce(int32_t kind, const dbhip_col* elems, const uint64_t*
   P.out_words = (unsigned long long*)out_validity;
   P.err_count = (unsigned long long*)err_count_dev;
   switch (ar_class(elems->type)) {
-    case AR_CLS_I: return two_passes(P, ar_reduce_kernel<AR_CLS_I>, ar_reduce_long_kernel<AR_CLS_I>, s, who);
-    case AR_CLS_U: return two_passes(P, ar_reduce_kernel<AR_CLS_U>, ar_reduce_long_kernel<AR_CLS_U>, s, who);
-    case AR_CLS_F32: return two_passes(P, ar_reduce_kernel<AR_CLS_F32>, ar_reduce_long_kernel<AR_CLS_F32>, s, who);
-    case AR_CLS_F64: return two_passes(P, ar_reduce_kernel<AR_CLS_F64>, ar_reduce_long_kernel<AR_CLS_F64>, s, who);
-    default: return two_passes(P, ar_reduce_kernel<AR_CLS_D128>, ar_reduce_long_kernel<AR_CLS_D128>, s, who);
+    case AR_CLS_I: return long_two_passes(P, ar_reduce_kernel<AR_CLS_I>, ar_reduce_long_kernel<AR_CLS_I>, AR_SCRATCH_SLOT, s, who);
+    case AR_CLS_U: return long_two_passes(P, ar_reduce_kernel<AR_CLS_U>, ar_reduce_long_kernel<AR_CLS_U>, AR_SCRATCH_SLOT, s, who);
+    case AR_CLS_F32: return long_two_passes(P, ar_reduce_kernel<AR_CLS_F32>, ar_reduce_long_kernel<AR_CLS_F32>, AR_SCRATCH_SLOT, s, who);
+    case AR_CLS_F64: return long_two_passes(P, ar_reduce_kernel<AR_CLS_F64>, ar_reduce_long_kernel<AR_CLS_F64>, AR_SCRATCH_SLOT, s, who);
+    default: return long_two_passes(P, ar_reduce_kernel<AR_CLS_D128>, ar_reduce_long_kernel<AR_CLS_D128>, AR_SCRATCH_SLOT, s, who);
   }
 }
 
@@ -634,7 +604,7 @@ int32_t dbhip_array_unnest_sel(const uint64_t* offsets, int64_t n, uint64_t n_el
   base_params(P, nullptr, offsets, n, n_elems);
   P.out_sel = out_sel;
   P.num_out = (uint64_t)num_out;
-  return two_passes(P, ar_unnest_kernel, ar_unnest_long_kernel, s, who);
+  return long_two_passes(P, ar_unnest_kernel, ar_unnest_long_kernel, AR_SCRATCH_SLOT, s, who);
 }
 
 }  // extern "C"

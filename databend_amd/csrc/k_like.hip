@@ -8,14 +8,15 @@
 //            aligned 4-byte loads that each cover at least one byte of the value (head and tail by shifting and masking), so nothing
 //            outside the value's own words is touched. The 64 result bits of a wave come from one __ballot and one lane stores them.
 //            A row longer than DBHIP_LIKE_LONG_BYTES that needs a search (CONTAINS, SEGMENTS) is not walked here: its row id goes
-//            into a list in scratch (one ballot and one atomic add per wave) and its bit is written as 0.
-//   pass 2   one wave per listed row, fixed grid, the count read on the device. The lanes try 64 consecutive start positions of a
+//            into the long-row list (dev_longrows.h) and its bit is written as 0.
+//   pass 2   one wave per listed row (dev_longrows.h). The lanes try 64 consecutive start positions of a
 //            segment at a time; the leftmost hit is picked from a __ballot and its end carried, wave-uniformly, to the next segment.
 //            A row that matches (after NEGATE) gets its bit with a 32-bit atomic OR; pass 1 has finished by then (same stream).
 // SEGMENTS runs the segments left to right, each at its leftmost match at or after the previous one's end: exact, because under
 // either unit definition a segment's end is monotone in its start. An end-anchored last segment is matched backwards from the end.
 #include <string.h>
 #include "dev_common.h"
+#include "dev_longrows.h"
 #include "dev_strview.h"
 #include "runtime.h"
 #define LIKE_FN __device__ __forceinline__
@@ -26,8 +27,6 @@ using namespace dbhip;
 namespace {
 
 constexpr int LIKE_SCRATCH_SLOT = 22;
-constexpr int LIKE_PASS2_BLOCKS = 512;       // fixed grid of pass 2: 2,048 waves that stride over the list
-constexpr int64_t LIKE_MAX_ROWS = 0xFFFFFFFELL;
 
 struct LikeParams {
   LikeTable t;
@@ -36,8 +35,7 @@ struct LikeParams {
   int64_t voff;
   const void* const* buffers;
   uint64_t* out;
-  uint32_t* long_count;
-  uint32_t* long_rows;
+  LongList list;
   int64_t n;
   int32_t n_buffers, negate, unit_byte, _pad;
 };
@@ -75,13 +73,7 @@ __global__ __launch_bounds__(256) void like_rows_kernel(const LikeParams P) {
       }
     }
     const uint64_t word = __ballot(bit);
-    const uint64_t lmask = __ballot(listed);
-    if (lmask) {                                // wave-uniform
-      uint32_t at = 0;
-      if (lane == 0) at = atomicAdd(P.long_count, (uint32_t)__popcll(lmask));
-      at = __shfl(at, 0, 64);
-      if (listed) P.long_rows[at + (uint32_t)__popcll(lmask & ((1ull << lane) - 1ull))] = (uint32_t)i;
-    }
+    list_rows(listed, lane, i, P.list);
     if (lane == 0) P.out[wave0 >> 6] = word;   // bits past n are 0: those lanes never set `bit`
   }
 }
@@ -93,11 +85,10 @@ __global__ __launch_bounds__(256) void like_long_kernel(const LikeParams P) {
   const uint32_t nseg = P.t.nseg;
   const bool a_start = P.t.anchor_start, a_end = P.t.anchor_end, unit_byte = P.unit_byte != 0;
   const uint32_t lane = threadIdx.x & 63;
-  const uint32_t count = *P.long_count;
-  const uint32_t nwaves = gridDim.x * 4;
+  const LongWalk lw = long_walk(P.list);
   const uint8_t* sb = (const uint8_t*)S.words;
-  for (uint32_t k = blockIdx.x * 4 + (threadIdx.x >> 6); k < count; k += nwaves) {
-    const uint32_t row = P.long_rows[k];
+  for (uint32_t q = lw.first; q < lw.count; q += lw.stride) {
+    const uint32_t row = P.list.rows[q];
     const uint4 vw = P.views[row];
     WaveValue v{vw.x, (const uint8_t*)P.buffers[vw.z] + vw.w};   // (a long view that pass 1 has checked: dev_strview.h sv_bytes_checked)
     // the anchored segments: every lane does the same work on the same bytes
@@ -153,7 +144,7 @@ __global__ __launch_bounds__(256) void like_fill_kernel(const uint64_t* one, uin
 int32_t like_run(const LikeTable& t, const dbhip_col* col, int32_t flags, int64_t n, uint8_t* out_bitmap, void* stream, const char* who) {
   if (!col || col->type != DBHIP_T_STRING) { set_error("%s: the column must be a String column", who); return DBHIP_ERR_INVALID; }
   if (flags & ~(DBHIP_LIKE_NEGATE | DBHIP_LIKE_UNIT_BYTE)) { set_error("%s: unknown flag bits", who); return DBHIP_ERR_INVALID; }
-  if (n < 0 || n > LIKE_MAX_ROWS) { set_error("%s: row count outside 0 .. 2^32 - 2", who); return DBHIP_ERR_INVALID; }
+  if (n < 0 || n > LONGROWS_MAX_ROWS) { set_error("%s: row count outside 0 .. 2^32 - 2", who); return DBHIP_ERR_INVALID; }
   if (n == 0) return DBHIP_OK;
   if (!col->data || !out_bitmap || ((uintptr_t)out_bitmap & 7) || ((uintptr_t)col->data & 15)) {
     set_error("%s: NULL views or bitmap, views not 16-byte aligned or bitmap not 8-byte aligned", who);
@@ -163,7 +154,7 @@ int32_t like_run(const LikeTable& t, const dbhip_col* col, int32_t flags, int64_
   const bool searches = t.nseg > 0 && (t.kind == DBHIP_LIKE_CONTAINS || t.kind == DBHIP_LIKE_SEGMENTS);   // only these list long rows
   const int64_t rows = col->is_scalar ? 1 : n;
   // scratch: count | (scalar: the one result word) | row ids
-  uint8_t* ws = (uint8_t*)scratch(64 + (searches ? (size_t)rows * 4 : 0) + 64, LIKE_SCRATCH_SLOT, s);
+  uint8_t* ws = (uint8_t*)scratch(long_list_bytes(searches ? rows : 0), LIKE_SCRATCH_SLOT, s);
   if (!ws) return DBHIP_ERR_HIP;
   LikeParams P;
   memset(&P, 0, sizeof(P));
@@ -174,17 +165,16 @@ int32_t like_run(const LikeTable& t, const dbhip_col* col, int32_t flags, int64_
   P.buffers = col->buffers;
   P.n_buffers = col->buffers && col->n_buffers > 0 ? col->n_buffers : 0;
   P.out = col->is_scalar ? (uint64_t*)(ws + 8) : (uint64_t*)out_bitmap;
-  P.long_count = (uint32_t*)ws;
-  P.long_rows = (uint32_t*)(ws + 64);
+  P.list = long_list_at(ws);
   P.n = rows;
   P.negate = (flags & DBHIP_LIKE_NEGATE) ? 1 : 0;
   P.unit_byte = (flags & DBHIP_LIKE_UNIT_BYTE) ? 1 : 0;
-  DBHIP_CHECK(hipMemsetAsync(ws, 0, 16, s));
+  DBHIP_CHECK(long_list_clear(ws, s));
   hipLaunchKernelGGL(like_rows_kernel, dim3(grid_for(rows, 256)), dim3(256), 0, s, P);
   DBHIP_LAUNCH_CHECK();
   if (searches) {
     DBHIP_POLL_CANCEL(s, who);
-    hipLaunchKernelGGL(like_long_kernel, dim3(LIKE_PASS2_BLOCKS), dim3(256), 0, s, P);
+    long_launch(like_long_kernel, P, s);
     DBHIP_LAUNCH_CHECK();
   }
   if (col->is_scalar) {

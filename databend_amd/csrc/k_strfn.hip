@@ -6,9 +6,9 @@
 //            long one through naturally aligned 4-byte loads that each cover a byte of the value (SfValue::byte). A slice result is
 //            a view again: 16 B in, 16 B out, and value bytes only where units or pads have to be looked at (byte mode: none, except
 //            the first four bytes of a long result that does not start at the value's start, and the bytes of a result that turns
-//            inline). A value longer than DBHIP_LIKE_LONG_BYTES that needs a walk is not walked here: its row id goes into a list
-//            in scratch (one ballot and one atomic add per wave) and its output is written as zero.
-//            pass 2: one wave per listed row, fixed grid, the count read on the device. A step is 64 aligned words (256 bytes): every
+//            inline). A value longer than DBHIP_LIKE_LONG_BYTES that needs a walk is not walked here: its row id goes into the
+//            long-row list (dev_longrows.h) and its output is written as zero.
+//            pass 2: one wave per listed row (dev_longrows.h). A step is 64 aligned words (256 bytes, dev_strwave.h): every
 //            lane marks the unit boundaries (or the pad mismatches) of its four bytes, ballots and popcounts find the k-th one.
 //   build    count (u32 bytes per row that go to out_data) -> dbscan::exclusive_scan_u32 -> fill: one lane per row writes the view (a
 //            result of up to 12 bytes from registers). The bytes of results of 13 .. DBHIP_LIKE_LONG_BYTES are copied by the row's own
@@ -19,6 +19,7 @@
 #include "dev_common.h"
 #include "dev_scan.h"
 #include "dev_strfn.h"
+#include "dev_strwave.h"
 #include "runtime.h"
 
 using namespace dbhip;
@@ -30,84 +31,8 @@ static_assert(SF_SUBSTR == DBHIP_STR_SUBSTR && SF_LEFT == DBHIP_STR_LEFT && SF_R
 namespace {
 
 constexpr int STRFN_SCRATCH_SLOT = 24;
-constexpr int STRFN_PASS2_BLOCKS = 512;        // fixed grid of the wave-per-row passes: 2,048 waves that stride over the list
-constexpr int64_t STRFN_MAX_ROWS = 0xFFFFFFFELL;
 
-struct StrCol {
-  const uint4* views;
-  const uint8_t* validity;
-  int64_t voff;
-  const void* const* buffers;
-  int32_t n_buffers, scalar;
-};
-
-StrCol str_col(const dbhip_col* c) {
-  StrCol s;
-  s.views = (const uint4*)c->data;
-  s.validity = c->validity;
-  s.voff = c->validity_offset;
-  s.buffers = c->buffers;
-  s.n_buffers = c->buffers && c->n_buffers > 0 ? c->n_buffers : 0;
-  s.scalar = c->is_scalar ? 1 : 0;
-  return s;
-}
-
-// row i of a column: false for a NULL row (*null_row) and for a long view that points nowhere; neither is dereferenced
-__device__ __forceinline__ bool str_value(const StrCol& c, int64_t i, SfValue& v, uint32_t& index, uint32_t& offset, bool& null_row) {
-  const int64_t r = c.scalar ? 0 : i;
-  null_row = c.validity && !bit_get(c.validity, c.voff + r);
-  if (null_row) return false;
-  const uint4 vw = c.views[r];
-  const uint8_t* bytes = nullptr;
-  if (!sv_bytes_checked(c.views + r, vw.x, vw.z, vw.w, c.buffers, c.n_buffers, &bytes)) return false;
-  v = sf_value(vw.x, vw.y, vw.z, vw.w, bytes);
-  index = vw.z;
-  offset = vw.w;
-  return true;
-}
-
-// ---- a long value as aligned words, for one wave -------------------------------------------------------------------------------------------
-struct WaveWords {
-  const uint32_t* words;   // the aligned word that holds the value's first byte
-  uint32_t lead, len, nwords;
-};
-__device__ __forceinline__ WaveWords ww_of(uintptr_t base, uint32_t len) {
-  WaveWords W;
-  W.lead = (uint32_t)(base & 3);
-  W.words = (const uint32_t*)(base - W.lead);
-  W.len = len;
-  W.nwords = (uint32_t)(((uint64_t)W.lead + len + 3) >> 2);
-  return W;
-}
-// word `widx` (only when it holds a byte of the value) and the 4-bit mask of its bytes whose positions lie in [lo, hi)
-__device__ __forceinline__ uint32_t ww_load(const WaveWords& W, int64_t widx, uint32_t lo, uint32_t hi, uint32_t& in) {
-  in = 0;
-  if (widx < 0 || widx >= (int64_t)W.nwords) return 0;
-  const int64_t p0 = widx * 4 - W.lead;
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (p0 + j >= (int64_t)lo && p0 + j < (int64_t)hi) in |= 1u << j;
-  return in ? W.words[widx] : 0u;
-}
-__device__ __forceinline__ uint32_t noncont4(uint32_t w) {   // bit j: byte j is not 10xxxxxx
-  const uint32_t nc = ~((w >> 7) & ~(w >> 6)) & 0x01010101u;
-  return (nc | (nc >> 7) | (nc >> 14) | (nc >> 21)) & 0xFu;
-}
-__device__ __forceinline__ uint64_t lanes_below(uint32_t lane) { return (1ull << lane) - 1ull; }
-__device__ __forceinline__ uint64_t lanes_above(uint32_t lane) { return lane == 63 ? 0ull : (~0ull << (lane + 1)); }
-
-// the boundaries of a step as four ballots; returns their number
-struct Ballots { uint64_t b[4]; };
-__device__ __forceinline__ uint32_t ballots_of(uint32_t bits, Ballots& B) {
-  uint32_t total = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { B.b[j] = __ballot((bits >> j) & 1u); total += (uint32_t)__popcll(B.b[j]); }
-  return total;
-}
-__device__ __forceinline__ uint32_t ballots_masked(const Ballots& B, uint64_t m) {
-  return (uint32_t)(__popcll(B.b[0] & m) + __popcll(B.b[1] & m) + __popcll(B.b[2] & m) + __popcll(B.b[3] & m));
-}
-
+// ---- the wave-per-row forms of dev_strfn.h's steps (the column frame and the word walk they use: dev_strwave.h) -------------------------------
 // sf_units for the wave
 __device__ __forceinline__ uint32_t wave_units(const WaveWords& W, uint32_t lane) {
   uint32_t acc = 0;
@@ -119,33 +44,6 @@ __device__ __forceinline__ uint32_t wave_units(const WaveWords& W, uint32_t lane
     acc += (uint32_t)__popc(bits);
   }
   return (uint32_t)wave_sum_u64(acc);
-}
-// sf_forward for the wave (k >= 1): the k-th boundary behind `from`, len when the value ends first
-__device__ __forceinline__ uint32_t wave_forward(const WaveWords& W, uint32_t from, uint32_t k, uint32_t lane) {
-  if (from + 1 >= W.len) return W.len;
-  uint32_t rem = k;
-  for (int64_t wb = ((int64_t)W.lead + from + 1) >> 2; wb < (int64_t)W.nwords; wb += 64) {      // wave-uniform bounds
-    const int64_t widx = wb + lane;
-    uint32_t in;
-    const uint32_t w = ww_load(W, widx, from + 1, W.len, in);
-    const uint32_t bits = noncont4(w) & in;
-    Ballots B;
-    const uint32_t total = ballots_of(bits, B);
-    if (rem <= total) {
-      const uint32_t before = ballots_masked(B, lanes_below(lane));
-      const bool hit = before < rem && rem <= before + (uint32_t)__popc(bits);
-      uint32_t pos = 0, r = rem - before;
-      if (hit) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if ((bits >> j) & 1u) { if (--r == 0) pos = (uint32_t)(widx * 4 + j - W.lead); }
-      }
-      const uint64_t hm = __ballot(hit);
-      return (uint32_t)__shfl((int)pos, __ffsll((unsigned long long)hm) - 1, 64);
-    }
-    rem -= total;
-  }
-  return W.len;
 }
 // sf_backward for the wave (m >= 1): the start of the m-th unit from the end
 __device__ __forceinline__ bool wave_backward(const WaveWords& W, uint32_t m, uint32_t lane, uint32_t* at) {
@@ -248,8 +146,7 @@ struct SliceParams {
   const int64_t *a, *b;
   uint4* out_views;       // slices
   uint64_t* out_len;      // length
-  uint32_t* long_count;
-  uint32_t* long_rows;
+  LongList list;
   int64_t n;
   int32_t op, unit_byte, a_scalar, b_scalar;
   uint32_t pad_len, _pad;
@@ -259,16 +156,6 @@ struct SliceParams {
 __device__ __forceinline__ void pad_stage(const SliceParams& P, uint32_t* s_pad) {   // 256 threads
   if (threadIdx.x < 64) s_pad[threadIdx.x] = P.pad[threadIdx.x];
   __syncthreads();
-}
-// one ballot and one atomic add per wave: the listed lanes' rows go into the list
-__device__ __forceinline__ void list_rows(bool listed, uint32_t lane, int64_t i, uint32_t* long_count, uint32_t* long_rows) {
-  const uint64_t lmask = __ballot(listed);
-  if (lmask) {                                // wave-uniform
-    uint32_t at = 0;
-    if (lane == 0) at = atomicAdd(long_count, (uint32_t)__popcll(lmask));
-    at = __shfl(at, 0, 64);
-    if (listed) long_rows[at + (uint32_t)__popcll(lmask & lanes_below(lane))] = (uint32_t)i;
-  }
 }
 
 // what a launch does: the instantiations keep the byte-mode slices (no value bytes to look at, nothing to list, no pad) and the byte
@@ -317,7 +204,7 @@ __global__ __launch_bounds__(256) void strfn_rows_kernel(const SliceParams P) {
         P.out_views[i] = make_uint4(w[0], w[1], w[2], w[3]);
       }
     }
-    if constexpr (lists) list_rows(listed, lane, i, P.long_count, P.long_rows);
+    if constexpr (lists) list_rows(listed, lane, i, P.list);
   }
 }
 
@@ -327,10 +214,9 @@ __global__ __launch_bounds__(256) void strfn_long_kernel(const SliceParams P) {
   __shared__ uint32_t s_pad[64];
   pad_stage(P, s_pad);
   const uint32_t lane = threadIdx.x & 63;
-  const uint32_t count = *P.long_count;
-  const uint32_t nwaves = gridDim.x * 4;
-  for (uint32_t k = blockIdx.x * 4 + (threadIdx.x >> 6); k < count; k += nwaves) {
-    const int64_t i = P.long_rows[k];
+  const LongWalk lw = long_walk(P.list);
+  for (uint32_t q = lw.first; q < lw.count; q += lw.stride) {
+    const int64_t i = P.list.rows[q];
     const int64_t r = P.col.scalar ? 0 : i;
     const uint4 vw = P.col.views[r];
     const uintptr_t base = (uintptr_t)P.col.buffers[vw.z] + vw.w;
@@ -361,7 +247,7 @@ int32_t check_string_col(const dbhip_col* c, const char* who) {
   return DBHIP_OK;
 }
 int32_t check_rows(int64_t n, const char* who) {
-  if (n < 0 || n > STRFN_MAX_ROWS) { set_error("%s: row count outside 0 .. 2^32 - 2", who); return DBHIP_ERR_INVALID; }
+  if (n < 0 || n > LONGROWS_MAX_ROWS) { set_error("%s: row count outside 0 .. 2^32 - 2", who); return DBHIP_ERR_INVALID; }
   return DBHIP_OK;
 }
 
@@ -370,17 +256,16 @@ int32_t slice_run(SliceParams& P, hipStream_t s, const char* who) {
   constexpr bool may_list = MODE == M_LENGTH_UNIT || MODE == M_PLAN_UNIT || MODE == M_TRIM;
   constexpr bool LENGTH = MODE == M_LENGTH_BYTE || MODE == M_LENGTH_UNIT;
   if (may_list) {
-    uint8_t* ws = (uint8_t*)scratch(64 + (size_t)P.n * 4 + 64, STRFN_SCRATCH_SLOT, s);
+    uint8_t* ws = (uint8_t*)scratch(long_list_bytes(P.n), STRFN_SCRATCH_SLOT, s);
     if (!ws) return DBHIP_ERR_HIP;
-    P.long_count = (uint32_t*)ws;
-    P.long_rows = (uint32_t*)(ws + 64);
-    DBHIP_CHECK(hipMemsetAsync(ws, 0, 16, s));
+    P.list = long_list_at(ws);
+    DBHIP_CHECK(long_list_clear(ws, s));
   }
   hipLaunchKernelGGL(strfn_rows_kernel<MODE>, dim3(grid_for(P.n, 256)), dim3(256), 0, s, P);
   DBHIP_LAUNCH_CHECK();
   if (may_list) {
     DBHIP_POLL_CANCEL(s, who);
-    hipLaunchKernelGGL(strfn_long_kernel<LENGTH>, dim3(STRFN_PASS2_BLOCKS), dim3(256), 0, s, P);
+    long_launch(strfn_long_kernel<LENGTH>, P, s);
     DBHIP_LAUNCH_CHECK();
   }
   return DBHIP_OK;
@@ -399,8 +284,7 @@ struct BuildParams {
   uint64_t out_data_bytes;
   uint64_t* out_validity;
   unsigned long long *err_count, *non_ascii;
-  uint32_t* long_count;
-  uint32_t* long_rows;
+  LongList list;
 };
 
 enum { ROW_DEAD = 0, ROW_EMPTY = 1, ROW_TOO_LONG = 2, ROW_OK = 3 };
@@ -516,7 +400,7 @@ __global__ __launch_bounds__(256) void strfn_fill_kernel(const BuildParams P) {
     }
     const uint64_t lives = __ballot(live);
     if (P.out_validity && lane == 0) P.out_validity[wave0 >> 6] = lives;    // bits past n are 0: those lanes are not live
-    list_rows(listed, lane, i, P.long_count, P.long_rows);
+    list_rows(listed, lane, i, P.list);
   }
   // every lane arrives here: one add per wave and counter
   errs = (uint32_t)wave_sum_u64(errs);
@@ -528,11 +412,10 @@ __global__ __launch_bounds__(256) void strfn_fill_kernel(const BuildParams P) {
 // one wave per listed row: its bytes fit (the fill kernel has checked), the result is longer than DBHIP_LIKE_LONG_BYTES
 __global__ __launch_bounds__(256) void strfn_copy_kernel(const BuildParams P) {
   const uint32_t lane = threadIdx.x & 63;
-  const uint32_t count = *P.long_count;
-  const uint32_t nwaves = gridDim.x * 4;
+  const LongWalk lw = long_walk(P.list);
   uint32_t highs = 0;
-  for (uint32_t k = blockIdx.x * 4 + (threadIdx.x >> 6); k < count; k += nwaves) {
-    const int64_t i = P.long_rows[k];
+  for (uint32_t q = lw.first; q < lw.count; q += lw.stride) {
+    const int64_t i = P.list.rows[q];
     if (wave_copy_row(P, i, P.out_data + P.offsets[i], lane) && lane == 0) ++highs;
   }
   if (lane == 0 && highs && P.non_ascii) atomicAdd(P.non_ascii, (unsigned long long)highs);
@@ -667,15 +550,14 @@ int32_t dbhip_str_build(int32_t op, const dbhip_col* args_host, int32_t nargs, i
   if (!ws) return DBHIP_ERR_HIP;
   P.counts = (uint32_t*)(ws + off_counts);
   P.offsets = (const uint64_t*)(ws + off_offsets);
-  P.long_count = (uint32_t*)ws;
-  P.long_rows = (uint32_t*)(ws + off_rows);
+  P.list = long_list_at(ws, 0, off_rows);
   P.out_views = (uint4*)out_views;
   P.out_data = out_data;
   P.out_data_bytes = out_data_bytes;
   P.out_validity = (uint64_t*)out_validity;
   P.err_count = (unsigned long long*)err_count_dev;
   P.non_ascii = (unsigned long long*)non_ascii_count_dev;
-  DBHIP_CHECK(hipMemsetAsync(ws, 0, 16, s));
+  DBHIP_CHECK(long_list_clear(ws, s));
   hipLaunchKernelGGL(strfn_count_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, P);
   DBHIP_LAUNCH_CHECK();
   DBHIP_POLL_CANCEL(s, who);
@@ -685,7 +567,7 @@ int32_t dbhip_str_build(int32_t op, const dbhip_col* args_host, int32_t nargs, i
   hipLaunchKernelGGL(strfn_fill_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, P);
   DBHIP_LAUNCH_CHECK();
   DBHIP_POLL_CANCEL(s, who);
-  hipLaunchKernelGGL(strfn_copy_kernel, dim3(STRFN_PASS2_BLOCKS), dim3(256), 0, s, P);
+  long_launch(strfn_copy_kernel, P, s);
   DBHIP_LAUNCH_CHECK();
   return DBHIP_OK;
 }

@@ -4,8 +4,8 @@
 // wave-per-row forms of the same steps. The structure is k_strfn.hip's:
 //   position / split_part   pass 1: one lane per row. The view is loaded as one 16-byte vector; a value of up to DBHIP_LIKE_LONG_BYTES is
 //            searched by its lane through naturally aligned 4-byte loads (SfValue::byte). A longer value that has to be searched is
-//            not: its row id goes into a list in scratch (one ballot and one atomic add per wave) and its output is written as zero.
-//            pass 2: one wave per listed row, fixed grid, the count read on the device.
+//            not: its row id goes into the long-row list (dev_longrows.h) and its output is written as zero.
+//            pass 2: one wave per listed row (dev_longrows.h), the value as aligned words (dev_strwave.h).
 //   rewrite  count (u32 bytes per row that go to out_data; long values that need a walk through the list and a wave-per-row count) ->
 //            dbscan::exclusive_scan_u32 -> fill: one lane per row writes the view of a result of up to 12 bytes from registers; results
 //            of 13 .. DBHIP_LIKE_LONG_BYTES are written by the row's own wave, one row after the other, so that neighbouring lanes
@@ -21,6 +21,7 @@
 #include "dev_common.h"
 #include "dev_scan.h"
 #include "dev_strsearch.h"
+#include "dev_strwave.h"
 #include "runtime.h"
 
 using namespace dbhip;
@@ -31,89 +32,8 @@ static_assert(SS_REPLACE == DBHIP_STRW_REPLACE && SS_LPAD == DBHIP_STRW_LPAD && 
 namespace {
 
 constexpr int SS_SCRATCH_SLOT = 27;
-constexpr int SS_PASS2_BLOCKS = 512;           // fixed grid of the wave-per-row passes: 2,048 waves that stride over the list
-constexpr int64_t SS_MAX_ROWS = 0xFFFFFFFELL;
 
-// ---- the column frame and a long value as aligned words: k_strfn.hip's, restated ---------------------------------------------------------
-struct StrCol {
-  const uint4* views;
-  const uint8_t* validity;
-  int64_t voff;
-  const void* const* buffers;
-  int32_t n_buffers, scalar;
-};
-StrCol str_col(const dbhip_col* c) {
-  StrCol s;
-  s.views = (const uint4*)c->data;
-  s.validity = c->validity;
-  s.voff = c->validity_offset;
-  s.buffers = c->buffers;
-  s.n_buffers = c->buffers && c->n_buffers > 0 ? c->n_buffers : 0;
-  s.scalar = c->is_scalar ? 1 : 0;
-  return s;
-}
-// row i of a column: false for a NULL row and for a long view that points nowhere; neither is dereferenced
-__device__ __forceinline__ bool str_value(const StrCol& c, int64_t i, SfValue& v, uint32_t& index, uint32_t& offset) {
-  const int64_t r = c.scalar ? 0 : i;
-  if (c.validity && !bit_get(c.validity, c.voff + r)) return false;
-  const uint4 vw = c.views[r];
-  const uint8_t* bytes = nullptr;
-  if (!sv_bytes_checked(c.views + r, vw.x, vw.z, vw.w, c.buffers, c.n_buffers, &bytes)) return false;
-  v = sf_value(vw.x, vw.y, vw.z, vw.w, bytes);
-  index = vw.z;
-  offset = vw.w;
-  return true;
-}
-// the bytes of row i for a wave: pass 1 has found the row usable. An inline value is read in place, in the view.
-__device__ __forceinline__ const uint8_t* str_bytes(const StrCol& c, int64_t i, uint4& vw) {
-  const int64_t r = c.scalar ? 0 : i;
-  vw = c.views[r];
-  return sv_is_inline(vw.x) ? (const uint8_t*)(c.views + r) + 4 : (const uint8_t*)c.buffers[vw.z] + vw.w;
-}
-
-struct WaveWords {
-  const uint32_t* words;   // the aligned word that holds the value's first byte
-  uint32_t lead, len, nwords;
-};
-__device__ __forceinline__ WaveWords ww_of(uintptr_t base, uint32_t len) {
-  WaveWords W;
-  W.lead = (uint32_t)(base & 3);
-  W.words = (const uint32_t*)(base - W.lead);
-  W.len = len;
-  W.nwords = (uint32_t)(((uint64_t)W.lead + len + 3) >> 2);
-  return W;
-}
-// word `widx` (only when it holds a byte of the value) and the 4-bit mask of its bytes whose positions lie in [lo, hi)
-__device__ __forceinline__ uint32_t ww_load(const WaveWords& W, int64_t widx, uint32_t lo, uint32_t hi, uint32_t& in) {
-  in = 0;
-  if (widx < 0 || widx >= (int64_t)W.nwords) return 0;
-  const int64_t p0 = widx * 4 - W.lead;
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (p0 + j >= (int64_t)lo && p0 + j < (int64_t)hi) in |= 1u << j;
-  return in ? W.words[widx] : 0u;
-}
-__device__ __forceinline__ uint32_t ww_byte(const WaveWords& W, uint32_t pos) {   // pos < len
-  const uint64_t a = (uint64_t)W.lead + pos;
-  return (W.words[a >> 2] >> (8 * (uint32_t)(a & 3))) & 0xFFu;
-}
-__device__ __forceinline__ uint32_t noncont4(uint32_t w) {   // bit j: byte j is not 10xxxxxx
-  const uint32_t nc = ~((w >> 7) & ~(w >> 6)) & 0x01010101u;
-  return (nc | (nc >> 7) | (nc >> 14) | (nc >> 21)) & 0xFu;
-}
-__device__ __forceinline__ uint64_t lanes_below(uint32_t lane) { return (1ull << lane) - 1ull; }
-__device__ __forceinline__ uint64_t lanes_from(uint32_t lane) { return lane >= 64 ? 0ull : (~0ull << lane); }
-
-struct Ballots { uint64_t b[4]; };
-__device__ __forceinline__ uint32_t ballots_of(uint32_t bits, Ballots& B) {
-  uint32_t total = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { B.b[j] = __ballot((bits >> j) & 1u); total += (uint32_t)__popcll(B.b[j]); }
-  return total;
-}
-__device__ __forceinline__ uint32_t ballots_masked(const Ballots& B, uint64_t m) {
-  return (uint32_t)(__popcll(B.b[0] & m) + __popcll(B.b[1] & m) + __popcll(B.b[2] & m) + __popcll(B.b[3] & m));
-}
+// ---- the column frame, a long value as aligned words and the long-row list: dev_strwave.h and dev_longrows.h -------------------------------
 // the unit boundaries at the positions [lo, hi) of the value, position 0 counted as one whatever its byte
 __device__ __forceinline__ uint32_t wave_bounds(const WaveWords& W, uint32_t lo, uint32_t hi, uint32_t lane) {
   uint32_t acc = 0;
@@ -128,44 +48,6 @@ __device__ __forceinline__ uint32_t wave_bounds(const WaveWords& W, uint32_t lo,
     acc += (uint32_t)__popc(bits);
   }
   return (uint32_t)wave_sum_u64(acc);
-}
-// sf_forward for the wave (k >= 1): the k-th boundary behind `from`, len when the value ends first
-__device__ __forceinline__ uint32_t wave_forward(const WaveWords& W, uint32_t from, uint32_t k, uint32_t lane) {
-  if (from + 1 >= W.len) return W.len;
-  uint32_t rem = k;
-  for (int64_t wb = ((int64_t)W.lead + from + 1) >> 2; wb < (int64_t)W.nwords; wb += 64) {
-    const int64_t widx = wb + lane;
-    uint32_t in;
-    const uint32_t w = ww_load(W, widx, from + 1, W.len, in);
-    const uint32_t bits = noncont4(w) & in;
-    Ballots B;
-    const uint32_t total = ballots_of(bits, B);
-    if (rem <= total) {
-      const uint32_t before = ballots_masked(B, lanes_below(lane));
-      const bool hit = before < rem && rem <= before + (uint32_t)__popc(bits);
-      uint32_t pos = 0, r = rem - before;
-      if (hit) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if ((bits >> j) & 1u) { if (--r == 0) pos = (uint32_t)(widx * 4 + j - W.lead); }
-      }
-      const uint64_t hm = __ballot(hit);
-      return (uint32_t)__shfl((int)pos, __ffsll((unsigned long long)hm) - 1, 64);
-    }
-    rem -= total;
-  }
-  return W.len;
-}
-
-// one ballot and one atomic add per wave: the listed lanes' rows go into the list
-__device__ __forceinline__ void list_rows(bool listed, uint32_t lane, int64_t i, uint32_t* long_count, uint32_t* long_rows) {
-  const uint64_t lmask = __ballot(listed);
-  if (lmask) {                                // wave-uniform
-    uint32_t at = 0;
-    if (lane == 0) at = atomicAdd(long_count, (uint32_t)__popcll(lmask));
-    at = __shfl(at, 0, 64);
-    if (listed) long_rows[at + (uint32_t)__popcll(lmask & lanes_below(lane))] = (uint32_t)i;
-  }
 }
 
 // ---- the wave's occurrence walk -------------------------------------------------------------------------------------------------------------
@@ -262,8 +144,7 @@ struct SearchParams {
   uint8_t* out_data;
   uint64_t out_data_bytes;
   unsigned long long* err_count;
-  uint32_t* long_count;
-  uint32_t* long_rows;
+  LongList list;
   int32_t op, unit_byte, k_scalar, _pad;
   SsConst C;
 };
@@ -297,7 +178,7 @@ __global__ __launch_bounds__(256) void ss_position_kernel(const SearchParams P) 
       }
       P.out_pos[i] = r;
     }
-    list_rows(listed, lane, i, P.long_count, P.long_rows);
+    list_rows(listed, lane, i, P.list);
   }
 }
 __global__ __launch_bounds__(256) void ss_position_long_kernel(const SearchParams P) {
@@ -305,10 +186,9 @@ __global__ __launch_bounds__(256) void ss_position_long_kernel(const SearchParam
   const_stage(P, S);
   const uint32_t lane = threadIdx.x & 63;
   const bool unit_byte = P.unit_byte != 0;
-  const uint32_t count = *P.long_count;
-  const uint32_t nwaves = gridDim.x * 4;
-  for (uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6); q < count; q += nwaves) {
-    const int64_t i = P.long_rows[q];
+  const LongWalk lw = long_walk(P.list);
+  for (uint32_t q = lw.first; q < lw.count; q += lw.stride) {
+    const int64_t i = P.list.rows[q];
     uint4 vw;
     const WaveWords W = ww_of((uintptr_t)str_bytes(P.col, i, vw), vw.x);
     const int64_t s = k_of(P, i, 1);                     // pass 1: 1 <= s <= len + 1
@@ -348,17 +228,16 @@ __global__ __launch_bounds__(256) void ss_split_kernel(const SearchParams P) {
       }
       P.out_views[i] = make_uint4(w[0], w[1], w[2], w[3]);
     }
-    list_rows(listed, lane, i, P.long_count, P.long_rows);
+    list_rows(listed, lane, i, P.list);
   }
 }
 __global__ __launch_bounds__(256) void ss_split_long_kernel(const SearchParams P) {
   __shared__ SsConst S;
   const_stage(P, S);
   const uint32_t lane = threadIdx.x & 63;
-  const uint32_t count = *P.long_count;
-  const uint32_t nwaves = gridDim.x * 4;
-  for (uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6); q < count; q += nwaves) {
-    const int64_t i = P.long_rows[q];
+  const LongWalk lw = long_walk(P.list);
+  for (uint32_t q = lw.first; q < lw.count; q += lw.stride) {
+    const int64_t i = P.list.rows[q];
     uint4 vw;
     const uint8_t* bytes = str_bytes(P.col, i, vw);
     const WaveWords W = ww_of((uintptr_t)bytes, vw.x);
@@ -423,7 +302,7 @@ __global__ __launch_bounds__(256) void ss_count_kernel(const SearchParams P) {
       if (P.counts) P.counts[i] = c;
       sum += c;
     }
-    list_rows(listed, lane, i, P.long_count, P.long_rows);
+    list_rows(listed, lane, i, P.list);
   }
   if (P.total) {      // every lane arrives here: one add per wave
     sum = wave_sum_u64(sum);
@@ -434,11 +313,10 @@ __global__ __launch_bounds__(256) void ss_count_long_kernel(const SearchParams P
   __shared__ SsConst S;
   const_stage(P, S);
   const uint32_t lane = threadIdx.x & 63;
-  const uint32_t count = *P.long_count;
-  const uint32_t nwaves = gridDim.x * 4;
+  const LongWalk lw = long_walk(P.list);
   uint64_t sum = 0;
-  for (uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6); q < count; q += nwaves) {
-    const int64_t i = P.long_rows[q];
+  for (uint32_t q = lw.first; q < lw.count; q += lw.stride) {
+    const int64_t i = P.list.rows[q];
     uint4 vw;
     const WaveWords W = ww_of((uintptr_t)str_bytes(P.col, i, vw), vw.x);
     const uint64_t total = wave_len(P, S, W, k_of(P, i, 0), lane);
@@ -605,7 +483,7 @@ __global__ __launch_bounds__(256) void ss_fill_kernel(const SearchParams P) {
       const int l = __ffsll((unsigned long long)cm) - 1;
       wave_fill_row(P, S, wave0 + l, __shfl(total, l, 64), __shfl(off, l, 64), lane);
     }
-    list_rows(listed, lane, i, P.long_count, P.long_rows);
+    list_rows(listed, lane, i, P.list);
   }
   errs = (uint32_t)wave_sum_u64(errs);                   // every lane arrives here: one add per wave
   if (lane == 0 && errs && P.err_count) atomicAdd(P.err_count, (unsigned long long)errs);
@@ -616,11 +494,10 @@ __global__ __launch_bounds__(256) void ss_fill_long_kernel(const SearchParams P)
   const_stage(P, S);
   const uint32_t lane = threadIdx.x & 63;
   const uint64_t cap = P.out_data_bytes < 0x100000000ull ? P.out_data_bytes : 0x100000000ull;
-  const uint32_t count = *P.long_count;
-  const uint32_t nwaves = gridDim.x * 4;
+  const LongWalk lw = long_walk(P.list);
   uint32_t errs = 0;
-  for (uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6); q < count; q += nwaves) {
-    const int64_t i = P.long_rows[q];
+  for (uint32_t q = lw.first; q < lw.count; q += lw.stride) {
+    const int64_t i = P.list.rows[q];
     const uint64_t total = P.lens[i];
     if (total == 0) continue;                            // (the view is zero already)
     const uint64_t off = total != SS_TOO_LONG && total > SV_INLINE_MAX ? P.offsets[i] : 0;
@@ -634,7 +511,7 @@ __global__ __launch_bounds__(256) void ss_fill_long_kernel(const SearchParams P)
 int32_t check_common(const dbhip_col* c, int32_t flags, int64_t n, const char* who) {
   if (!c || c->type != DBHIP_T_STRING) { set_error("%s: the column must be a String column", who); return DBHIP_ERR_INVALID; }
   if (flags & ~DBHIP_STR_UNIT_BYTE) { set_error("%s: unknown flag bits", who); return DBHIP_ERR_INVALID; }
-  if (n < 0 || n > SS_MAX_ROWS) { set_error("%s: row count outside 0 .. 2^32 - 2", who); return DBHIP_ERR_INVALID; }
+  if (n < 0 || n > LONGROWS_MAX_ROWS) { set_error("%s: row count outside 0 .. 2^32 - 2", who); return DBHIP_ERR_INVALID; }
   return DBHIP_OK;
 }
 int32_t check_const(const uint8_t* p, int32_t len, const char* what, const char* who) {
@@ -657,21 +534,6 @@ void base_params(SearchParams& P, const dbhip_col* col, const dbhip_col* k, int6
   if (k) { P.k = (const int64_t*)k->data; P.k_scalar = k->is_scalar ? 1 : 0; }
   P.n = n;
   P.unit_byte = (flags & DBHIP_STR_UNIT_BYTE) ? 1 : 0;
-}
-// pass 1 and the wave-per-row pass over its list
-template <class K1, class K2>
-int32_t two_passes(SearchParams& P, K1 rows_kernel, K2 long_kernel, hipStream_t s, const char* who) {
-  uint8_t* ws = (uint8_t*)scratch(64 + (size_t)P.n * 4 + 64, SS_SCRATCH_SLOT, s);
-  if (!ws) return DBHIP_ERR_HIP;
-  P.long_count = (uint32_t*)ws;
-  P.long_rows = (uint32_t*)(ws + 64);
-  DBHIP_CHECK(hipMemsetAsync(ws, 0, 16, s));
-  hipLaunchKernelGGL(rows_kernel, dim3(grid_for(P.n, 256)), dim3(256), 0, s, P);
-  DBHIP_LAUNCH_CHECK();
-  DBHIP_POLL_CANCEL(s, who);
-  hipLaunchKernelGGL(long_kernel, dim3(SS_PASS2_BLOCKS), dim3(256), 0, s, P);
-  DBHIP_LAUNCH_CHECK();
-  return DBHIP_OK;
 }
 // the arguments of dbhip_str_rewrite_bytes / dbhip_str_rewrite that the two share
 int32_t rewrite_params(int32_t op, const dbhip_col* col, const dbhip_col* k, const uint8_t* x, int32_t x_len, const uint8_t* y, int32_t y_len,
@@ -712,7 +574,7 @@ int32_t dbhip_str_position(const dbhip_col* col, const uint8_t* needle_host, int
   base_params(P, col, start, n, flags);
   P.out_pos = out;
   ss_prepare(P.C, needle_host, (uint32_t)needle_len, nullptr, 0, P.unit_byte != 0);
-  return two_passes(P, ss_position_kernel, ss_position_long_kernel, s, who);
+  return long_two_passes(P, ss_position_kernel, ss_position_long_kernel, SS_SCRATCH_SLOT, s, who);
 }
 
 int32_t dbhip_str_split_part(const dbhip_col* col, const uint8_t* delim_host, int32_t delim_len, const dbhip_col* part, int64_t n,
@@ -732,7 +594,7 @@ int32_t dbhip_str_split_part(const dbhip_col* col, const uint8_t* delim_host, in
   base_params(P, col, part, n, 0);
   P.out_views = (uint4*)out_views;
   ss_prepare(P.C, delim_host, (uint32_t)delim_len, nullptr, 0, true);
-  return two_passes(P, ss_split_kernel, ss_split_long_kernel, s, who);
+  return long_two_passes(P, ss_split_kernel, ss_split_long_kernel, SS_SCRATCH_SLOT, s, who);
 }
 
 int32_t dbhip_str_rewrite_bytes(int32_t op, const dbhip_col* col, const dbhip_col* k, const uint8_t* x_host, int32_t x_len, const uint8_t* y_host,
@@ -745,17 +607,15 @@ int32_t dbhip_str_rewrite_bytes(int32_t op, const dbhip_col* col, const dbhip_co
   *out_bytes_host = 0;
   if (n == 0) return DBHIP_OK;
   hipStream_t s = resolve_stream(stream);
-  P.total = nullptr;
-  uint8_t* ws = (uint8_t*)scratch(64 + (size_t)n * 4 + 64, SS_SCRATCH_SLOT, s);
+  uint8_t* ws = (uint8_t*)scratch(long_list_bytes(n), SS_SCRATCH_SLOT, s);
   if (!ws) return DBHIP_ERR_HIP;
-  P.long_count = (uint32_t*)ws;
+  P.list = long_list_at(ws);
   P.total = (unsigned long long*)(ws + 8);
-  P.long_rows = (uint32_t*)(ws + 64);
-  DBHIP_CHECK(hipMemsetAsync(ws, 0, 16, s));
+  DBHIP_CHECK(long_list_clear(ws, s));
   hipLaunchKernelGGL(ss_count_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, P);
   DBHIP_LAUNCH_CHECK();
   DBHIP_POLL_CANCEL(s, who);
-  hipLaunchKernelGGL(ss_count_long_kernel, dim3(SS_PASS2_BLOCKS), dim3(256), 0, s, P);
+  long_launch(ss_count_long_kernel, P, s);
   DBHIP_LAUNCH_CHECK();
   uint64_t* host = pinned_words(0);
   DBHIP_CHECK(hipMemcpyAsync(host, ws + 8, 8, hipMemcpyDeviceToHost, s));
@@ -790,24 +650,22 @@ int32_t dbhip_str_rewrite(int32_t op, const dbhip_col* col, const dbhip_col* k, 
   P.out_data = out_data;
   P.out_data_bytes = out_data_bytes;
   P.err_count = (unsigned long long*)err_count_dev;
-  P.long_count = (uint32_t*)ws;
-  P.long_rows = (uint32_t*)(ws + off_rows_a);
-  DBHIP_CHECK(hipMemsetAsync(ws, 0, 16, s));
+  P.list = long_list_at(ws, 0, off_rows_a);
+  DBHIP_CHECK(long_list_clear(ws, s));
   hipLaunchKernelGGL(ss_count_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, P);
   DBHIP_LAUNCH_CHECK();
   DBHIP_POLL_CANCEL(s, who);
-  hipLaunchKernelGGL(ss_count_long_kernel, dim3(SS_PASS2_BLOCKS), dim3(256), 0, s, P);
+  long_launch(ss_count_long_kernel, P, s);
   DBHIP_LAUNCH_CHECK();
   DBHIP_POLL_CANCEL(s, who);
   const int32_t src = dbscan::exclusive_scan_u32(P.counts, n, (uint64_t*)(ws + off_blk), (uint64_t*)(ws + off_offsets), s);
   if (src) return src;
   DBHIP_POLL_CANCEL(s, who);
-  P.long_count = (uint32_t*)(ws + 4);
-  P.long_rows = (uint32_t*)(ws + off_rows_b);
+  P.list = long_list_at(ws, 1, off_rows_b);
   hipLaunchKernelGGL(ss_fill_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, P);
   DBHIP_LAUNCH_CHECK();
   DBHIP_POLL_CANCEL(s, who);
-  hipLaunchKernelGGL(ss_fill_long_kernel, dim3(SS_PASS2_BLOCKS), dim3(256), 0, s, P);
+  long_launch(ss_fill_long_kernel, P, s);
   DBHIP_LAUNCH_CHECK();
   return DBHIP_OK;
 }
